@@ -10,7 +10,12 @@ Before the W warm-up steps an untimed set-up phase keeps the kernel running for 
 MI355X needs ~50 ms of work to reach its steady clock (profiles/r01/clock_ramp_series.txt); the timed region is still
 exactly K steps.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+A plain run does only what the headline needs: set-up, clock ramp, W warm-up steps, the K timed steps, the line (`value`, `ms_per_step`
+and the `roofline` figures derived from the timed region's events).  --full adds every untimed diagnostic described below, after the
+timed region and in the same order as before; the --no-* options switch single diagnostics of a --full run off.  --dump-outputs DIR
+writes a fixed, seeded sample of the planes the last timed step produced as float32 .npy files (dump_outputs), so that two builds run
+with the same arguments can be compared output for output.
 For N > 1 the driver launches one rank per GPU through torch.distributed.run; ranks never exchange pixels
 (row tiles are independent -- SURVEY.md 8e), torch.distributed (RCCL) only provides the barrier and the
 MAX-over-ranks of the timed region.  --scaling strong (default): ONE 8192 x 8192 frame is cut into N even-row tiles, rank k
@@ -20,18 +25,18 @@ image.  --scaling weak: every rank converts one full frame per step (a batch of 
 FRESH DATA (round 5): the plug-in converts every byte once, so the timed region never touches the same buffer twice within the
 reach of the 256-MiB Infinity Cache: the K steps ROTATE over >= 4 disjoint (frame, planes) sets whose footprints add up to > 1 GB
 (`roofline.buffer_sets`).  A benchmark loop that re-converts ONE frame measures the cache for every load that allocates there; that
-figure is kept beside the claimed one as `roofline.frac_same_buffers` (untimed diagnostic pass).
+figure is kept beside the claimed one as `roofline.frac_same_buffers` (untimed diagnostic pass of --full).
 
 Rank 0 prints ONE JSON line.  `roofline.achieved` = algorithmic bytes per launch (18 B/px: 12 in + 6 out,
 SURVEY.md 8d) / mean kernel time from HIP events recorded on the launch stream around the K rotating launches; `roofline.peak` =
-the 8 TB/s spec, `roofline.peak_measured` = what the kernel's MATH-FREE twin (same loads and stores with the same cache policy, no
+the 8 TB/s spec; with --full, `roofline.peak_measured` = what the kernel's MATH-FREE twin (same loads and stores with the same cache policy, no
 conversion) reaches over the same rotating sets in the same process IN THE FASTEST OF SIX LAUNCH SHAPES (workgroups of 4 / 2 / 1 waves,
 buffer or 64-bit global addressing: `pattern_shapes_ms`; the kernel's own shape is the slowest of them, so round 1-4's figure --
 kept as `frac_of_twin_in_kernel_shape` -- flattered the kernel), `frac_of_measured` = achieved / that; `read_only_frac` is the north-star's literal "HBM-read" figure (input bytes
 only), bounded by 12/18 for 4:4:4 output -- `frac` is the one that is claimed.  `roofline.traffic` = HBM bytes per launch from
-the PMC counters, measured in THIS run at N = 1 by two child `rocprofv3 --pmc` passes over the same kernel (measure_traffic_live;
-about 25 s; --no-live-traffic or a missing rocprofv3 falls back to the committed profiles/traffic.json, and the line says which).
-Extra objects on the same line:
+the PMC counters, measured in a --full run at N = 1 by two child `rocprofv3 --pmc` passes over the same kernel (measure_traffic_live;
+about 25 s; a plain run, --no-live-traffic or a missing rocprofv3 falls back to the committed profiles/traffic.json, and the line says which).
+Extra objects on the --full line:
   c5              BASELINE.json configs[4] (16384 x 16384 RGBA f32 -> 12-bit PQ Y,Cb,Cr,A), the same N-way row split, device-resident
   pcie_inclusive  rank 0 alone, ONE process, the library's in-process row-tile scheduler on the N GPUs of the run
                   (avifgpu_init_devices): page-locked host rows in, host planes out -- what N x16 links buy this path
@@ -76,6 +81,46 @@ def make_frame(torch, dev, width, height, planes, seed):
     a = torch.where(m < 0.10, hi, a)                       # ~10 % highlights in (1, 12.5]
     a = torch.where(m > 0.999, -0.01 * a, a)               # ~0.1 % small negatives
     return a.view(height, width * planes).contiguous()
+
+
+DUMP_SAMPLES = 1 << 22          # samples per plane --dump-outputs writes at most: 3 planes x 4 Mi x 4 B = 48 MiB
+DUMP_SEED = 20240601
+
+
+def dump_positions(h, w, budget, plane_index, seed=DUMP_SEED):
+    """Where --dump-outputs samples an (h, w) plane larger than `budget` samples: (rows, points) -- half the budget in whole rows (the
+    first, the last and seeded others: every column, edges included), the rest in seeded flat indices anywhere.  Depends on the seed
+    and the shape only, so two builds run with the same arguments sample the same positions."""
+    import numpy as np
+    rng = np.random.default_rng([seed, plane_index])
+    nr = min(h, budget // 2 // w)
+    pick = [0, h - 1][:nr] + rng.choice(np.arange(1, h - 1), size=max(0, nr - 2), replace=False).tolist()
+    rows = np.unique(np.array(pick, dtype=np.int64))
+    points = rng.integers(0, h * w, size=budget - len(rows) * w)
+    return rows, points
+
+
+def dump_outputs(directory, planes, rank, world):
+    """--dump-outputs: what the last timed step handed its caller -- the Y, Cb, Cr planes of 16-bit codes -- as float32 .npy files.
+    A plane that fits the budget is written whole (`<plane>.npy`); a larger one as `<plane>_rows.npy` and `<plane>_points.npy`
+    (dump_positions).  N > 1: each rank writes its own row tile, names prefixed `rank<k>_`, within a 1/N share of the budget."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    budget = DUMP_SAMPLES // world
+    prefix = f"rank{rank}_" if world > 1 else ""
+    for pi, (name, p) in enumerate(zip(("y", "cb", "cr"), planes)):
+        codes = p.view(torch.int16)                                    # (rows, samples): 16-bit little-endian codes, <= 12 bits used
+        h, w = codes.shape
+        if h * w <= budget:
+            arrays = {name: codes}
+        else:
+            rows, points = dump_positions(h, w, budget, pi)
+            arrays = {name + "_points": codes.reshape(-1)[torch.from_numpy(points).to(codes.device)]}
+            if len(rows):
+                arrays[name + "_rows"] = codes[torch.from_numpy(rows).to(codes.device)]
+        for key, t in arrays.items():
+            np.save(os.path.join(directory, prefix + key + ".npy"), t.to(torch.float32).cpu().numpy())
 
 
 def measure_traffic_live(args, kernel_name):
@@ -268,7 +313,14 @@ def main():
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="do not measure roofline.traffic in this run (two child rocprofv3 --pmc passes); use profiles/traffic.json")
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)   # the child of those passes: the kernel alone, 24 launches
+    ap.add_argument("--full", action="store_true",
+                    help="also run every diagnostic beside the headline (cold launch, isolated / batched launches, one-set loop, compact PQ, "
+                         "math-free twin, live PMC traffic, c5, c2 ... open_d8, PCIe-inclusive, cpu_baseline); the --no-* options apply to these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write a fixed seeded sample of the planes the last timed step produced to DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     import torch
     import __graft_entry__ as entry
@@ -339,16 +391,20 @@ def main():
         nset = max(4, int(-(-args.min_footprint_gb * 1e9 // algo_bytes)))
         nset = min(nset, 64)
     sets = [(src, ptrs)]
+    set_planes = [planes]                      # the plane tensors behind each set's pointers (--dump-outputs reads them)
     keep = []
     for j in range(1, 2 if args.traffic_child and nset > 1 else nset):
         f = src.clone()
         pl = [torch.empty_like(t) for t in planes]
         keep.append((f, pl))
+        set_planes.append(pl)
         sets.append((f, [t.data_ptr() for t in pl] + [None]))
     torch.cuda.synchronize(dev)
+    last_set = [0]                             # the set the latest step() wrote
 
     def step(same=False):
-        sj, pj = sets[0] if same else sets[launches[0] % len(sets)]
+        last_set[0] = 0 if same else launches[0] % len(sets)
+        sj, pj = sets[last_set[0]]
         launches[0] += 1
         gpu.write_rows(desc, row0, nrows, sj.data_ptr(), sj.stride(0) * 4, pj, strides,
                        mem=pkg.MEM_DEVICE, stream=stream.cuda_stream)
@@ -380,7 +436,7 @@ def main():
     # untimed diagnostic, BEFORE any ramp: what a plug-in save pays -- ONE launch on a GPU that has been idle.  The first launch of the
     # process also loads the code object; the second figure is the same launch after the device has idled for a second again.
     cold = None
-    if not args.no_cold:
+    if args.full and not args.no_cold:
         def one_launch():
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t1 = time.perf_counter()
@@ -423,28 +479,34 @@ def main():
     # barrier + synchronize, K steps, synchronize + barrier, MAX over ranks (avif-format_amd/distrib.py)
     elapsed = ranks.timed(timed_step, args.steps, sync=lambda: torch.cuda.synchronize(dev))
     mean_kernel_s = ev0.elapsed_time(ev1) / args.steps / 1e3
-
-    # untimed diagnostic pass: per-launch event pairs for the spread (isolated launches; not used for value / roofline)
-    nd = min(args.steps, 100)
-    starts = [torch.cuda.Event(enable_timing=True) for _ in range(nd)]
-    ends = [torch.cuda.Event(enable_timing=True) for _ in range(nd)]
-    for i in range(nd):
-        starts[i].record(stream)
-        step()
-        ends[i].record(stream)
-    torch.cuda.synchronize(dev)
-    series = [s.elapsed_time(e) for s, e in zip(starts, ends)]
-    if os.environ.get("AVIFGPU_BENCH_SERIES"):
-        print("series_ms " + " ".join(f"{t:.4f}" for t in series), file=sys.stderr, flush=True)
-    kernel_ms = sorted(series)
     kernel_name = gpu.last_kernel()
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, set_planes[last_set[0]], rank, world)
+
+    # ---- from here on every `if args.full` block is an untimed diagnostic: a plain run skips them all and prints the headline ----
+    # untimed diagnostic pass: per-launch event pairs for the spread (isolated launches; not used for value / roofline)
+    kernel_ms = None
+    if args.full:
+        nd = min(args.steps, 100)
+        starts = [torch.cuda.Event(enable_timing=True) for _ in range(nd)]
+        ends = [torch.cuda.Event(enable_timing=True) for _ in range(nd)]
+        for i in range(nd):
+            starts[i].record(stream)
+            step()
+            ends[i].record(stream)
+        torch.cuda.synchronize(dev)
+        series = [s.elapsed_time(e) for s, e in zip(starts, ends)]
+        if os.environ.get("AVIFGPU_BENCH_SERIES"):
+            print("series_ms " + " ".join(f"{t:.4f}" for t in series), file=sys.stderr, flush=True)
+        kernel_ms = sorted(series)
 
     # untimed diagnostic: the same K back-to-back launches on ONE buffer set -- the loop every benchmark writes, and what rounds 1-4
     # reported.  What it gains over the timed region is what the Infinity Cache gives a frame that is converted again before 256 MiB of
     # other traffic has passed: nothing a save ever sees.  (Loads with the non-temporal hint do not allocate there and gain nothing;
     # loads that allocate normally do -- round 4's cached edge loads read 3 % faster in this loop and 3 % slower on fresh data.)
     same_buffers = None
-    if len(sets) > 1:
+    if args.full and len(sets) > 1:
         for _ in range(40):
             step(same=True)
         torch.cuda.synchronize(dev)
@@ -462,7 +524,7 @@ def main():
     # 99.99 % / 99.96 % (tests/test_gpu_t2_truth.py) -- parity was taken over what it costs: between -1 % and +5 % box to box
     # (profiles/r05/probe_shapes_and_kernel_shapes.txt, pq_compact_vs_close_two_boxes.txt).
     pq_compact = None
-    if args.transfer == "pq" and not args.no_pattern:
+    if args.full and args.transfer == "pq" and not args.no_pattern:
         dc = pkg.WriteDesc(width=W, height=H, depth=32, planes=3, bit_depth=args.bits, transfer=pkg.TRANSFER_PQ, peak_nits=80,
                            alpha_state=pkg.ALPHA_NONE, output=pkg.OUT_YCBCR, chroma=chroma, matrix_coefficients=pkg.MATRIX_BT2020_NCL,
                            color_primaries=pkg.PRIMARIES_BT2020, pq_evaluation=pkg.PQ_COMPACT)
@@ -491,7 +553,7 @@ def main():
     # Its rate is what this box's memory system gives this access pattern on fresh data right now: the MEASURED ceiling next to the
     # nominal 8 TB/s.
     pattern = None
-    if args.chroma == "444" and W % 512 == 0 and not args.no_pattern:
+    if args.full and args.chroma == "444" and W % 512 == 0 and not args.no_pattern:
         import ctypes
         lib = pkg.load()
         P3, S3 = ctypes.c_void_p * 3, ctypes.c_int64 * 3
@@ -536,22 +598,26 @@ def main():
             pattern = {"error": str(exc)}
 
     # untimed diagnostic: percentiles over back-to-back BATCHES of 10 launches (one event pair per batch: no per-launch gap)
-    nb = max(10, min(args.steps // 10, 40))
-    bev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(nb)]
-    for a, b in bev:
-        a.record(stream)
-        for _ in range(10):
-            step()
-        b.record(stream)
-    torch.cuda.synchronize(dev)
-    batch_ms = sorted(a.elapsed_time(b) / 10 for a, b in bev)
+    batch_ms = None
+    if args.full:
+        nb = max(10, min(args.steps // 10, 40))
+        bev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(nb)]
+        for a, b in bev:
+            a.record(stream)
+            for _ in range(10):
+                step()
+            b.record(stream)
+        torch.cuda.synchronize(dev)
+        batch_ms = sorted(a.elapsed_time(b) / 10 for a, b in bev)
 
     # what every rank measured on its own GPU (one SCALE record then answers "which GPU was slow" and "does a 1/N tile take 1/N of
     # the time": the launch floor of DESIGN.md section 6.5 says no -- 0.89 strong-scaling efficiency projected at N = 8)
-    per_rank = ranks.gather_objects({"rank": rank, "device": dev_index, "rows": nrows, "kernel_ms_mean": round(mean_kernel_s * 1e3, 5),
-                                     "GB_s": round(gpu.write_algorithmic_bytes(desc, nrows) / mean_kernel_s / 1e9, 1),
-                                     "batches_of_10_ms_p50": round(batch_ms[len(batch_ms) // 2], 5),
-                                     "pci_bus_id": (gpu.topology() or [{}])[0].get("pci_bus_id"), "numa_node": (gpu.topology() or [{}])[0].get("numa_node")})
+    mine = {"rank": rank, "device": dev_index, "rows": nrows, "kernel_ms_mean": round(mean_kernel_s * 1e3, 5),
+            "GB_s": round(gpu.write_algorithmic_bytes(desc, nrows) / mean_kernel_s / 1e9, 1)}
+    if batch_ms:
+        mine["batches_of_10_ms_p50"] = round(batch_ms[len(batch_ms) // 2], 5)
+    mine.update({"pci_bus_id": (gpu.topology() or [{}])[0].get("pci_bus_id"), "numa_node": (gpu.topology() or [{}])[0].get("numa_node")})
+    per_rank = ranks.gather_objects(mine)
     total_rows = H * world if args.scaling == "weak" else H
     total_px = float(W) * total_rows * args.steps
     value = total_px / elapsed / 1e6
@@ -592,14 +658,16 @@ def main():
                                     f"{algo_bytes * (len(sets) - 1) / 1e9:.2f} GB of other traffic (Infinity Cache: 0.27 GB)" if len(sets) > 1
                                     else "ONE set (--no-rotate): loads that allocate in the Infinity Cache re-read it; not a fresh-data figure"},
             "kernel_ms_mean": round(mean_kernel_s * 1e3, 5),
-            "isolated_launch_ms_p10_p50_p90": [round(kernel_ms[int(len(kernel_ms) * q)], 5) for q in (0.1, 0.5, 0.9)],
-            "batches_of_10_ms_p10_p50_p90": [round(batch_ms[int(len(batch_ms) * q)], 5) for q in (0.1, 0.5, 0.9)],
             # the north-star's literal "HBM-READ roofline": input bytes only.  Bounded by 12/18 = 0.667 for 4:4:4 output (a third of the
             # kernel's traffic is stores), so `frac` -- all bytes moved, reads and writes -- is the figure that is claimed
             "read_only_frac": round((12.0 * W * nrows) / mean_kernel_s / 1e9 / HBM_PEAK_GBPS, 4),
             "read_only_frac_upper_bound": round(12.0 / 18.0, 4) if args.chroma == "444" else None,
         },
     }
+    if kernel_ms:
+        out["roofline"]["isolated_launch_ms_p10_p50_p90"] = [round(kernel_ms[int(len(kernel_ms) * q)], 5) for q in (0.1, 0.5, 0.9)]
+    if batch_ms:
+        out["roofline"]["batches_of_10_ms_p10_p50_p90"] = [round(batch_ms[int(len(batch_ms) * q)], 5) for q in (0.1, 0.5, 0.9)]
     if pattern and "kernel_ms_mean" in pattern:
         peak_measured = algo_bytes / (pattern["kernel_ms_mean"] / 1e3) / 1e9
         out["roofline"]["peak_measured"] = round(peak_measured, 1)
@@ -633,7 +701,7 @@ def main():
     # PMC-derived HBM traffic per launch: NOT measured in this run (counters need their own rocprofv3 --pmc passes, which the
     # driver's plain run cannot do) -- read from the committed summary of those passes and labelled as such
     live = None
-    if world == 1 and not args.no_live_traffic:
+    if args.full and world == 1 and not args.no_live_traffic:
         live = measure_traffic_live(args, kernel_name)
     if live and live.get("hbm_bytes_per_launch"):
         out["roofline"]["traffic"] = live["hbm_bytes_per_launch"]
@@ -654,7 +722,7 @@ def main():
     del sets[1:], keep[:]                      # the copies' memory back before C5 and the host-pointer job
 
     # ---- configs[4]: 16384^2 RGBA f32 -> 12-bit PQ Y,Cb,Cr,A, the same N-way row split (device-resident) ----
-    if not args.no_c5:
+    if args.full and not args.no_c5:
         W5 = H5 = 16384
         d5 = pkg.WriteDesc(width=W5, height=H5, depth=32, planes=4, bit_depth=12, transfer=pkg.TRANSFER_PQ, peak_nits=80,
                            alpha_state=pkg.ALPHA_STRAIGHT, output=pkg.OUT_YCBCR, chroma=pkg.CHROMA_444,
@@ -683,12 +751,13 @@ def main():
         del f5, p5
 
     # ---- the other BASELINE configurations and the default saves / opens (N = 1: each needs the whole GPU's memory system to itself) ----
-    if world == 1 and not args.no_extra_configs:
+    if args.full and world == 1 and not args.no_extra_configs:
         out.update(extra_configs(torch, pkg, gpu, dev, stream, args.steps))
 
     # ---- PCIe-inclusive: ONE process (rank 0), the library's in-process scheduler on the N GPUs of this run ----
-    ranks.barrier()
-    if rank == 0 and not args.no_pcie:
+    if args.full:
+        ranks.barrier()
+    if args.full and rank == 0 and not args.no_pcie:
         ndev = torch.cuda.device_count()
         if ndev >= world:
             try:
@@ -756,9 +825,10 @@ def main():
                 out["pcie_inclusive"] = {"value": None, "note": f"skipped: {exc}"}
         else:
             out["pcie_inclusive"] = {"value": None, "note": f"skipped: {ndev} device(s) visible to rank 0, {world} needed"}
-    ranks.host_barrier()          # the other ranks waited here on the CPU: their GPUs were rank 0's to use
+    if args.full:
+        ranks.host_barrier()      # the other ranks waited here on the CPU: their GPUs were rank 0's to use
 
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         if not args.no_cpu_baseline:
             import ctypes
             import harness

@@ -25,7 +25,7 @@ def test_bench_line_is_a_fresh_data_figure():
 
 def _bench_line_checks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "80", "--warmup", "5", "--no-cpu-baseline", "--no-pcie", "--no-c5",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "80", "--warmup", "5", "--no-cpu-baseline", "--no-pcie", "--no-c5",
                         "--no-live-traffic", "--no-cold", "--clock-ramp-ms", "60"], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -1,7 +1,7 @@
 #!/bin/bash
-# bench.py with the live PMC traffic measurement: the line, how long the whole command took, and the child mode alone
+# bench.py --full with the live PMC traffic measurement: the line, how long the whole command took, and the child mode alone
 out=gpurun_out/live_traffic; mkdir -p $out
-t0=$(date +%s.%N); python bench.py > $out/bench.json 2> $out/bench.err; t1=$(date +%s.%N)
+t0=$(date +%s.%N); python bench.py --full > $out/bench.json 2> $out/bench.err; t1=$(date +%s.%N)
 python - <<PY
 import json
 d=json.load(open("$out/bench.json"))
