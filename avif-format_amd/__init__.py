@@ -110,6 +110,49 @@ class IccShaper8(ctypes.Structure):
                 ("shaper2", (ctypes.c_uint8 * 16388) * 3)]
 
 
+ICC_PIPE_MAX_STAGES, ICC_PIPE_MAX_CURVE, ICC_PIPE_MAX_GRID = 16, 4096, 33
+ICC_PIPE_MAX_WORDS = 33 * 33 * 33 * 3 + 4 * 3 * 4096
+ICC_STAGE_CURVES, ICC_STAGE_MATRIX, ICC_STAGE_CLUT16, ICC_STAGE_LAB_TO_XYZ, ICC_STAGE_XYZ_TO_LAB = 1, 2, 3, 4, 5
+
+
+class IccStage32(ctypes.Structure):
+    _fields_ = [("kind", c_int32), ("curve_type", c_int32 * 3), ("entries", c_int32 * 3), ("offset", c_int32 * 3),
+                ("has_bias", c_int32), ("reserved", c_int32), ("params", (ctypes.c_double * 10) * 3),
+                ("matrix", ctypes.c_double * 9), ("bias", ctypes.c_double * 3)]
+
+
+class IccPipeline32(ctypes.Structure):
+    """lcms2's float stage program of a 32-bit document behind a LUT-based profile (include/avifgpu.h, avifgpu_icc_pipeline32)."""
+    _fields_ = [("target", c_int32), ("stage_count", c_int32), ("word_count", c_int32), ("reserved", c_int32),
+                ("proof", ctypes.c_uint64), ("stages", IccStage32 * ICC_PIPE_MAX_STAGES),
+                ("words", ctypes.c_uint16 * ICC_PIPE_MAX_WORDS)]
+
+
+LCMS_BRIDGE_PATH = os.path.join(_HERE, "libavifgpu_lcms_bridge.so")
+
+
+def lcms_bridge():
+    """integration/LcmsTableBridge.cpp, built next to the library where lcms2.h exists (None otherwise).  It resolves avifgpu_*
+    against the already loaded library."""
+    if not os.path.exists(LCMS_BRIDGE_PATH):
+        return None
+    load()
+    B = ctypes.CDLL(LCMS_BRIDGE_PATH)
+    B.avifgpu_lcms_document_to_pipeline32.restype = c_int32
+    B.avifgpu_lcms_document_to_pipeline32.argtypes = [c_void_p, ctypes.c_uint32, c_int32, c_int32, POINTER(IccPipeline32)]
+    return B
+
+
+def icc_pipeline32_from_profile(profile_bytes: bytes, target=ICC_TARGET_REC2020_LINEAR, has_alpha=False):
+    """(OSErr, IccPipeline32): the proven stage program the adapter builds for a document profile (bridge above; None if absent)."""
+    B = lcms_bridge()
+    if B is None:
+        return None
+    t = IccPipeline32()
+    rc = B.avifgpu_lcms_document_to_pipeline32(profile_bytes, len(profile_bytes), target, 1 if has_alpha else 0, ctypes.byref(t))
+    return rc, t
+
+
 class DeviceInfo(ctypes.Structure):
     _fields_ = [("device", c_int32), ("numa_node", c_int32), ("workers", c_int32), ("workers_pinned", c_int32),
                 ("pci_bus_id", ctypes.c_char * 32), ("cpulist", ctypes.c_char * 256)]
@@ -160,6 +203,10 @@ ABI = [
     ("avifgpu_icc_prepare_shaper8", c_int32, [c_void_p, ctypes.c_uint32, POINTER(IccShaper8)]),
     ("avifgpu_write_rows_icc8", c_int32, [POINTER(WriteDesc), POINTER(IccShaper8), c_int32, c_int32, c_void_p, c_int64,
                                           POINTER(_PLANES4), POINTER(_STRIDES4), c_int32, c_void_p]),
+    ("avifgpu_icc_pipeline32_prove", c_int32, [POINTER(IccPipeline32), c_void_p, c_void_p]),
+    ("avifgpu_icc_pipeline32_eval", c_int32, [POINTER(IccPipeline32), c_void_p, c_void_p, ctypes.c_uint32]),
+    ("avifgpu_write_rows_icc_pipeline32", c_int32, [POINTER(WriteDesc), POINTER(IccPipeline32), c_int32, c_int32, c_void_p, c_int64,
+                                                    POINTER(_PLANES4), POINTER(_STRIDES4), c_int32, c_void_p]),
     ("avifgpu_get_yuv_coefficients", c_int32, [c_int32, c_int32, c_int32, POINTER(c_float * 3)]),
     ("avifgpu_read_max_value", c_int32, [POINTER(ReadDesc)]),
     ("avifgpu_write_plane_count", c_int32, [POINTER(WriteDesc)]),
@@ -274,6 +321,11 @@ class AvifGpu:
             self._check(self.lib.avifgpu_write_rows_icc16(ctypes.byref(desc), ctypes.byref(icc), row0, nrows, src_ptr, src_row_bytes,
                                                           ctypes.byref(planes4(dst_ptrs)), ctypes.byref(strides4(dst_strides)),
                                                           mem, stream or None))
+            return
+        if isinstance(icc, IccPipeline32):
+            self._check(self.lib.avifgpu_write_rows_icc_pipeline32(ctypes.byref(desc), ctypes.byref(icc), row0, nrows, src_ptr, src_row_bytes,
+                                                                   ctypes.byref(planes4(dst_ptrs)), ctypes.byref(strides4(dst_strides)),
+                                                                   mem, stream or None))
             return
         if isinstance(icc, IccSampled32):
             self._check(self.lib.avifgpu_write_rows_icc_sampled(ctypes.byref(desc), ctypes.byref(icc), row0, nrows, src_ptr, src_row_bytes,

@@ -170,6 +170,7 @@ struct IccDeviceTables {
     void* icc16 = nullptr; std::vector<uint8_t> icc16_host;    // 33^3 x 4 u16
     void* pow_tab = nullptr;                                    // 128 x float4, constant
     void* s32 = nullptr;   std::vector<uint8_t> s32_host;      // 3 x 65536 floats: sampled curves of a 32-bit document
+    void* p32 = nullptr;   std::vector<uint8_t> p32_host;      // stage records + words of a 32-bit document's stage program (icc = 8)
     // the caller's table of the last upload and a fingerprint of it: a tile that passes the same struct again (every tile of an image
     // does) skips the byte-for-byte comparison of 216-792 KiB under g_icc_mu.  A prepared table is immutable while it is in use
     // (include/avifgpu.h); the fingerprint -- 4096 strided words -- is the guard against a caller that rewrites one in place anyway,
@@ -400,6 +401,40 @@ int upload_icc8(const avifgpu_icc_shaper8* t, WriteParams& p)
     return 0;
 }
 
+// The stage program of a 32-bit document (icc = 8): its stage records, then its words (padded: the kernel copies whole dwords to LDS).  Small
+// -- a 17^3 program is ~36 KiB -- so every call compares the caller's program with the device copy outright and re-uploads on any difference:
+// a program rewritten at the same address between two saves is never served stale.
+int upload_icc_pipeline32(const avifgpu_icc_pipeline32* t, WriteParams& p)
+{
+    constexpr size_t kRecBytes = sizeof(avifgpu_icc_stage32) * AVIFGPU_ICC_PIPE_MAX_STAGES;
+    constexpr size_t kCap = kRecBytes + sizeof(t->words) + 16;
+    const size_t rec = sizeof(avifgpu_icc_stage32) * (size_t)t->stage_count, words = (size_t)t->word_count * 2;
+    std::vector<uint8_t> blob(kRecBytes + ((words + 15) & ~(size_t)15), 0);
+    memcpy(blob.data(), t->stages, rec);
+    memcpy(blob.data() + kRecBytes, t->words, words);
+    int dev = -1;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return hip_fail(e, "hipGetDevice", AVIFGPU_writErr);
+    std::lock_guard<std::mutex> lk(g_icc_mu);
+    IccDeviceTables& c = g_icc_tables[dev];
+    if (!c.p32) {
+        e = hipMalloc(&c.p32, kCap);
+        if (e != hipSuccess) { c.p32 = nullptr; return hip_fail(e, "hipMalloc(ICC stage program)", AVIFGPU_memFullErr); }
+    }
+    if (c.p32_host != blob) {
+        e = hipDeviceSynchronize();                             // a launch may still be reading the previous program
+        if (e == hipSuccess) e = hipMemcpy(c.p32, blob.data(), blob.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return hip_fail(e, "upload of the ICC stage program", AVIFGPU_writErr);
+        c.p32_host.swap(blob);
+    }
+    p.icc_p8_stages = c.p32;
+    p.icc_p8_words = reinterpret_cast<const uint16_t*>(static_cast<const uint8_t*>(c.p32) + kRecBytes);
+    p.icc_p8_nstages = t->stage_count;
+    p.icc_p8_lds_words = (words <= 48u * 1024u && !(g_hot_variant & 64)) ? t->word_count : 0;    // bit 6: tests take the memory path
+    for (int ch = 0; ch < 3; ++ch) p.icc_trc_type[ch] = 8;
+    return 0;
+}
+
 // avifgpu_shutdown: nothing is in flight any more.
 void release_device_caches()
 {
@@ -413,6 +448,7 @@ void release_device_caches()
         if (kv.second.icc16) (void)hipFree(kv.second.icc16);
         if (kv.second.pow_tab) (void)hipFree(kv.second.pow_tab);
         if (kv.second.s32) (void)hipFree(kv.second.s32);
+        if (kv.second.p32) (void)hipFree(kv.second.p32);
     }
     g_icc_tables.clear();
     if (cur >= 0) (void)hipSetDevice(cur);
@@ -453,6 +489,15 @@ int fill_write_params(const avifgpu_write_desc* d, int row0, int nrows, const Wr
     const avifgpu_icc_transform* g_icc = icc.s32 ? &icc.s32->base : icc.f32;
     const avifgpu_icc_clut16* g_icc16 = icc.c16;
     const avifgpu_icc_shaper8* g_icc8 = icc.s8;
+    if (icc.p32) {
+        if (d->depth != 32 || d->planes < 3) return fail(AVIFGPU_formatBadParameters, "the ICC stage program applies to 32-bit RGB(A) documents");
+        if (g_icc) return fail(AVIFGPU_formatBadParameters, "one ICC transform per call");
+        // the reference converts to sRGB only for the SDR save of a 32-bit document (ColorProfileConversion.cpp:118-123)
+        if (icc.p32->target == AVIFGPU_ICC_TARGET_SRGB_FLOAT && d->transfer != AVIFGPU_TRANSFER_CLIP)
+            return fail(AVIFGPU_formatBadParameters, "the sRGB ICC target goes with transfer Clip");
+        const int rc = upload_icc_pipeline32(icc.p32, p);
+        if (rc) return rc;
+    }
     if (g_icc) {
         if (d->depth != 32 || d->planes < 3) return fail(AVIFGPU_formatBadParameters, "the ICC row transform applies to 32-bit RGB(A) documents");
         if (icc.s32) {
@@ -917,6 +962,17 @@ int32_t avifgpu_write_rows_icc8_table(const avifgpu_write_desc* d, const avifgpu
                                       int32_t mem_kind, void* stream)
 {
     IccArgs a; a.c8t = icc;
+    return write_rows_any(d, a, row0, nrows, src, src_row_bytes, dst, dst_stride, mem_kind, stream);
+}
+
+int32_t avifgpu_write_rows_icc_pipeline32(const avifgpu_write_desc* d, const avifgpu_icc_pipeline32* icc, int32_t row0, int32_t nrows,
+                                          const void* src, int64_t src_row_bytes, void* const dst[4], const int64_t dst_stride[4],
+                                          int32_t mem_kind, void* stream)
+{
+    g_err[0] = 0;
+    if (icc && !icc_pipeline32_stamped(icc))
+        return fail(AVIFGPU_formatBadParameters, "the ICC stage program is not proven: unstamped, or altered since avifgpu_icc_pipeline32_prove");
+    IccArgs a; a.p32 = icc;
     return write_rows_any(d, a, row0, nrows, src, src_row_bytes, dst, dst_stride, mem_kind, stream);
 }
 

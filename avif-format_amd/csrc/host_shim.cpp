@@ -118,7 +118,7 @@ struct WritePlan { avifgpu_write_desc desc; int output; };
 // the tile loop that replaces WriteHeifImage.cpp:1017-1135 (and its five siblings).
 void CreateHeifImageInto(FormatRecordPtr formatRecord, AlphaState alphaState, const VPoint& imageSize,
                          const SaveUIOptions& callerOptions, int output, int matrix, int primaries, avifgpu_image* img,
-                         const avifgpu_icc_clut16* documentToSRGB16 = nullptr)
+                         const avifgpu_icc_clut16* documentToSRGB16 = nullptr, const avifgpu_icc_pipeline32* documentPipeline = nullptr)
 {
     const bool hasAlpha = alphaState != AlphaState::None;
     const bool mono = IsMonochromeImage(formatRecord);
@@ -181,6 +181,22 @@ void CreateHeifImageInto(FormatRecordPtr formatRecord, AlphaState alphaState, co
     avifgpu_icc_transform icc;
     const avifgpu_icc_transform* iccp = nullptr;
     std::unique_ptr<avifgpu_icc_sampled32> iccs;                // 32-bit document with sampled curves (792 KiB: on the heap)
+    const avifgpu_icc_pipeline32* iccPipe = nullptr;            // 32-bit document behind a LUT-based profile: the caller's proven stage program
+    // Neither parse took the profile: the caller's program, if it was built for this very decision, else the refusal goes back to the
+    // caller (who keeps lcms2).  A program for the other target is refused outright -- its proof was run against another transform.
+    auto take_pipeline = [&](int rc, int32_t target) -> int {
+        if (rc != AVIFGPU_formatCannotRead || !documentPipeline) return rc;
+        if (documentPipeline->target != target) {
+            avifgpu::set_error("the ICC stage program was built for another target than this save converts to");
+            throw OSErrException(AVIFGPU_formatBadParameters);
+        }
+        if (!avifgpu::icc_pipeline32_stamped(documentPipeline)) {
+            avifgpu::set_error("the ICC stage program is not proven: unstamped, or altered since avifgpu_icc_pipeline32_prove");
+            throw OSErrException(AVIFGPU_formatBadParameters);
+        }
+        iccPipe = documentPipeline;
+        return AVIFGPU_noErr;
+    };
     if (saveOptions.convertToRec2020) {
         if (formatRecord->depth != 32 || mono || !formatRecord->iCCprofileData || formatRecord->iCCprofileSize <= 0)
             throw OSErrException(AVIFGPU_formatBadParameters);
@@ -191,8 +207,9 @@ void CreateHeifImageInto(FormatRecordPtr formatRecord, AlphaState alphaState, co
             rc = avifgpu_icc_prepare_sampled(formatRecord->iCCprofileData, (uint32_t)formatRecord->iCCprofileSize,
                                              AVIFGPU_ICC_TARGET_REC2020_LINEAR, iccs.get());
             if (rc) iccs.reset();
+            rc = take_pipeline(rc, AVIFGPU_ICC_TARGET_REC2020_LINEAR);
         } else if (!rc) iccp = &icc;
-        if (rc) throw OSErrException((OSErr)rc);       // e.g. LUT-based profile: the caller falls back to its lcms2 path
+        if (rc) throw OSErrException((OSErr)rc);       // e.g. LUT-based profile without a program: the caller falls back to its lcms2 path
     }
     // ... and for the 8-bit SDR case (document profile -> sRGB, ColorProfileConversion.cpp:134-157): lcms2's own 8-bit
     // matrix-shaper integer pipeline, bit-exact
@@ -209,6 +226,7 @@ void CreateHeifImageInto(FormatRecordPtr formatRecord, AlphaState alphaState, co
             rc = avifgpu_icc_prepare_sampled(formatRecord->iCCprofileData, (uint32_t)formatRecord->iCCprofileSize,
                                              AVIFGPU_ICC_TARGET_SRGB_FLOAT, iccs.get());
             if (rc) iccs.reset();
+            rc = take_pipeline(rc, AVIFGPU_ICC_TARGET_SRGB_FLOAT);
         } else if (!rc) iccp = &icc;
         if (rc) throw OSErrException((OSErr)rc);
     } else if (saveOptions.convertToSRGB && formatRecord->depth == 16) {
@@ -238,6 +256,7 @@ void CreateHeifImageInto(FormatRecordPtr formatRecord, AlphaState alphaState, co
     avifgpu::IccArgs iccArgs;
     iccArgs.f32 = iccp; iccArgs.s8 = icc8.get(); iccArgs.c16 = icc16 ? icc16.get() : (saveOptions.convertToSRGB && formatRecord->depth == 16 ? documentToSRGB16 : nullptr); iccArgs.s32 = iccs.get();
     iccArgs.c8t = (saveOptions.convertToSRGB && formatRecord->depth == 8 && !icc8) ? documentToSRGB16 : nullptr;
+    iccArgs.p32 = iccPipe;
 
     // Every exit path drains the contexts: no tile may still be reading a pinned buffer or writing a plane afterwards.
     auto bail = [&](OSErr e) { (void)avifgpu::wait_all(); formatRecord->data = nullptr; throw OSErrException(e); };
@@ -445,10 +464,10 @@ avifgpu_OSErr avifgpu_host_create_heif_image(avifgpu_FormatRecord* formatRecord,
                                                      nullptr, img);
 }
 
-avifgpu_OSErr avifgpu_host_create_heif_image_with_table(avifgpu_FormatRecord* formatRecord, int32_t alphaState,
-                                                        const avifgpu_SaveUIOptions* saveOptions, int32_t output,
-                                                        int32_t matrix_coefficients, int32_t color_primaries,
-                                                        const avifgpu_icc_clut16* documentToSRGB16, avifgpu_image* img)
+static avifgpu_OSErr create_heif_image(avifgpu_FormatRecord* formatRecord, int32_t alphaState, const avifgpu_SaveUIOptions* saveOptions,
+                                       int32_t output, int32_t matrix_coefficients, int32_t color_primaries,
+                                       const avifgpu_icc_clut16* documentToSRGB16, const avifgpu_icc_pipeline32* documentPipeline,
+                                       avifgpu_image* img)
 {
     if (!formatRecord || !saveOptions || !img || !formatRecord->advanceState) return AVIFGPU_formatBadParameters;
     if (matrix_coefficients < 0) {                          // "what the plug-in will attach"
@@ -465,8 +484,24 @@ avifgpu_OSErr avifgpu_host_create_heif_image_with_table(avifgpu_FormatRecord* fo
         default: throw OSErrException(AVIFGPU_formatBadParameters);
         }
         CreateHeifImageInto(formatRecord, (AlphaState)alphaState, imageSize, *saveOptions, output, matrix_coefficients,
-                            color_primaries, img, documentToSRGB16);
+                            color_primaries, img, documentToSRGB16, documentPipeline);
     }, AVIFGPU_writErr);
+}
+
+avifgpu_OSErr avifgpu_host_create_heif_image_with_table(avifgpu_FormatRecord* formatRecord, int32_t alphaState,
+                                                        const avifgpu_SaveUIOptions* saveOptions, int32_t output,
+                                                        int32_t matrix_coefficients, int32_t color_primaries,
+                                                        const avifgpu_icc_clut16* documentToSRGB16, avifgpu_image* img)
+{
+    return create_heif_image(formatRecord, alphaState, saveOptions, output, matrix_coefficients, color_primaries, documentToSRGB16, nullptr, img);
+}
+
+avifgpu_OSErr avifgpu_host_create_heif_image_with_pipeline(avifgpu_FormatRecord* formatRecord, int32_t alphaState,
+                                                           const avifgpu_SaveUIOptions* saveOptions, int32_t output,
+                                                           int32_t matrix_coefficients, int32_t color_primaries,
+                                                           const avifgpu_icc_pipeline32* documentPipeline, avifgpu_image* img)
+{
+    return create_heif_image(formatRecord, alphaState, saveOptions, output, matrix_coefficients, color_primaries, nullptr, documentPipeline, img);
 }
 
 avifgpu_OSErr avifgpu_host_read_heif_image(const avifgpu_image* image, int32_t alphaState, const avifgpu_nclx* nclxProfile,

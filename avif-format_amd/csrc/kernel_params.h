@@ -103,6 +103,12 @@ struct WriteParams {
     int32_t icc_s_n[3];           // their entry counts; 0 = look curve[] up in memory (or a parametric channel, see icc_s_par)
     int32_t icc_s_par;            // bit c: channel c of a MIXED profile carries a parametric curve (icc_trc_f[c], evaluated like icc = 2); the rest are sampled
     int32_t icc_s_lds;            // the sampled channels' tables go to LDS (every one of them has icc_s_n > 0)
+    // lcms2's float stage program of a 32-bit document behind a LUT-based profile (avifgpu_icc_pipeline32), icc = 8: the stage records
+    // (avifgpu_icc_stage32) and the words they index, in device memory; icc_trc_type[] = 8 marks it for the launchers
+    const void*     icc_p8_stages;
+    const uint16_t* icc_p8_words;
+    int32_t icc_p8_nstages;
+    int32_t icc_p8_lds_words;     // words[] copied to LDS per workgroup (the program's tables fit 48 KiB); 0 = read from device memory
 };
 
 struct ReadParams {

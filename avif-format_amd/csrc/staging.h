@@ -19,6 +19,7 @@ struct IccArgs {
     const avifgpu_icc_clut16*    c16 = nullptr;     // 16-bit documents (avifgpu_write_rows_icc16)
     const avifgpu_icc_sampled32* s32 = nullptr;     // 32-bit documents with sampled curves (avifgpu_write_rows_icc_sampled)
     const avifgpu_icc_clut16*    c8t = nullptr;     // 8-bit documents behind a LUT-based profile: the 33^3 table (avifgpu_write_rows_icc8_table)
+    const avifgpu_icc_pipeline32* p32 = nullptr;    // 32-bit documents behind a LUT-based profile: lcms2's stage program (avifgpu_write_rows_icc_pipeline32)
 };
 
 constexpr int kLabelBytes = 192;                    // kernel label buffers handed to launch_*()
@@ -32,6 +33,8 @@ int  hip_fail(hipError_t e, const char* what, int code);
 void set_error(const char* msg);
 const char* last_error();
 void set_last_kernel(const char* label);
+// ---- icc_pipeline32.cpp ----------------------------------------------------------------------------------------------
+bool icc_pipeline32_stamped(const avifgpu_icc_pipeline32* p);      // proven, and unchanged since
 
 int  check_write(const avifgpu_write_desc* d, int row0, int nrows, WriteGeom& g);
 int  check_write_buffers(const avifgpu_write_desc* d, const WriteGeom& g, int nrows, const void* src, int64_t src_row_bytes,

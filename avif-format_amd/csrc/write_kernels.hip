@@ -24,6 +24,7 @@
 #include "staging.h"
 #include "device_math.h"
 #include "satword_f32.h"
+#include "icc_pipeline32.h"
 #include "../../include/avifgpu.h"
 
 #pragma clang fp contract(off)
@@ -40,20 +41,23 @@ namespace avifgpu {
 //        hand-off as a copy);  3  RGB f32 4:2:2 / 4:2:0, RGBA f32 and Gray32 + alpha streaming kernels
 //    8, 16   write_px, the generic kernel, for 8- and 16-bit documents
 //    32  write_px for gray (+ alpha) f32 documents (the fall-back of their streaming kernels), 33 for RGB(A) f32 documents (the fall-back of the streaming kernels
-//        and the parametric-curve ICC variants), 36 write_px<32, ..., icc = 6>: documents whose profile carries sampled curves
+//        and the parametric-curve ICC variants), 36 write_px<32, ..., icc = 6>: documents whose profile carries sampled curves, 38 write_px<32, ..., icc = 8>:
+//        documents behind a LUT-based profile (lcms2's float stage program)
 //    0   everything in one object (tools/ab_variants.sh builds its A/B libraries that way).
 // A kernel is emitted where a launch of it is instantiated; the launchers of a part are compiled in that part only (kHere* below), the
 // streaming part reaches the others through the four launch_planes_* functions.
 #ifndef AG_WRITE_PART
 #define AG_WRITE_PART 0
 #endif
-constexpr bool kHerePlain  = AG_WRITE_PART != 36 && AG_WRITE_PART != 1;     // write_px without icc = 6 (of the depth of the part)
+constexpr bool kHerePlain  = AG_WRITE_PART != 36 && AG_WRITE_PART != 38 && AG_WRITE_PART != 1;     // write_px without icc = 6 / 8 (of the depth of the part)
 constexpr bool kHereIcc6   = AG_WRITE_PART == 0 || AG_WRITE_PART == 36;
+constexpr bool kHereIcc8   = AG_WRITE_PART == 0 || AG_WRITE_PART == 38;
 hipError_t launch_planes_d8(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, hipStream_t st, char* label);
 hipError_t launch_planes_d16(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, hipStream_t st, char* label);
 hipError_t launch_planes_d32(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, hipStream_t st, char* label);
 hipError_t launch_planes_d32_rgb(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, hipStream_t st, char* label);
 hipError_t launch_planes_d32_icc6(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, hipStream_t st, char* label);
+hipError_t launch_planes_d32_icc8(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, hipStream_t st, char* label);
 
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 #ifndef AG_ICC_F32
@@ -500,6 +504,20 @@ AG_DEV void icc_apply_sampled(const WriteParams& p, float (&c)[3])
     }
 }
 
+// ICC = 8: a 32-bit document behind a LUT-based (A2B) profile.  lcms2 does not resample for float formatters: cmsDoTransform evaluates the
+// linked pipeline stage by stage, a float between stages -- the program avifgpu_icc_pipeline32 carries.  The stages are icc_pipeline32.h, the
+// same definitions the proof ran on the host: curves and matrices in double (the library's expression order, no folding -- it rounds to float
+// between stages), the 16-bit words of table curves and of the CLUT with quick_saturate_word_f32, TetrahedralInterp16 on the grid.  The
+// program is uniform across the launch; one pixel runs it in a call of its own, so the (pow-heavy) stage code exists once in the kernel
+// rather than once per pixel of the footprint.  Words come from LDS when they fit (write_px copies them), else from device memory.
+struct Icc8Px { float r, g, b; };
+__device__ __noinline__ Icc8Px icc8_eval_pixel(const avifgpu_icc_stage32* __restrict__ stages, int nstages, const uint16_t* words, Icc8Px x)
+{
+    float v[3] = { x.r, x.g, x.b };
+    for (int i = 0; i < nstages; ++i) icc32::stage(stages[i], words, v);
+    return Icc8Px{ v[0], v[1], v[2] };
+}
+
 #ifndef AG_ICC16_LEAN
 #define AG_ICC16_LEAN 1
 #endif
@@ -658,8 +676,8 @@ AG_DEV void stage_a(const WriteParams& p, const uint32_t (&s)[PLANES], uint32_t 
         float col[NCOL];
 #pragma unroll
         for (int k = 0; k < NCOL; ++k) col[k] = __uint_as_float(s[k]);
-        if constexpr (ICC != 0 && COLOR) {                                                        // ConvertRow runs before the pixel loop: WriteHeifImage.cpp:1031-1034
-            if constexpr (ICC == 6) icc_apply_sampled(p, col);
+        if constexpr (ICC != 0 && ICC != 8 && COLOR) {                                            // ConvertRow runs before the pixel loop: WriteHeifImage.cpp:1031-1034
+            if constexpr (ICC == 6) icc_apply_sampled(p, col);                                    // (icc = 8: write_px ran the whole program already)
             else if constexpr (IccF32<ICC>::value) icc_apply_f<ICC>(p, *iccRegs, *iccRegsF, powTf, col);
             else icc_apply<ICC>(p, *iccRegs, powT, col);
         }
@@ -831,7 +849,7 @@ template <bool DST16, int PLANES, int XS, int ICC = 0> struct WriteShape {
     // ICC == 5 (the 16-bit table transform) saved to u8 planes: 4 chroma samples per lane like the u16 layouts.  With 8, a 4:2:0 footprint
     // is 32 pixels x two 16-byte gathers each, all hoisted: 315 VGPRs = ONE wave per SIMD (profiles/r02/isa/resources.tsv); with 4 it is
     // 16 pixels and the kernel fits 3-4 waves.
-    static constexpr int NC = ((ICC == 2 || ICC == 4 || ((ICC == 5 || ICC == 7) && AG_ICC_TAB_NC2)) && XS == 1) ? 2 : ((DST16 && ICC == 0) ? AG_W16_NC : ((DST16 || ICC == 5 || ICC == 7) ? 4 : ((PLANES == 2 || PLANES == 4) ? AG_W8_NC_ALPHA : AG_W8_NC)));
+    static constexpr int NC = ((ICC == 2 || ICC == 4 || ICC == 8 || ((ICC == 5 || ICC == 7) && AG_ICC_TAB_NC2)) && XS == 1) ? 2 : ((DST16 && ICC == 0) ? AG_W16_NC : ((DST16 || ICC == 5 || ICC == 7) ? 4 : ((PLANES == 2 || PLANES == 4) ? AG_W8_NC_ALPHA : AG_W8_NC)));
     static constexpr int PXT = NC << XS;
 };
 
@@ -912,6 +930,19 @@ __global__ __launch_bounds__(AG_WPX_BLOCK) void write_px(const WriteParams p)
                 for (int i = threadIdx.x; i < n; i += AG_WPX_BLOCK) icc6_pairs[icc6_off[ch] + i] = (uint32_t)t16[i] | ((uint32_t)t16[min(i + 1, n - 1)] << 16);
             }
             __syncthreads();
+        }
+    }
+
+    // stage-program ICC variant: the program's words (curve tables, CLUT grid) in the same dynamic LDS when they fit (p.icc_p8_lds_words)
+    const uint16_t* icc8_words = nullptr;
+    if constexpr (ICC == 8) {
+        icc8_words = p.icc_p8_words;
+        if (p.icc_p8_lds_words) {
+            const uint32_t* g32 = reinterpret_cast<const uint32_t*>(p.icc_p8_words);     // the device copy is padded to 16 bytes
+            const int n32 = (p.icc_p8_lds_words + 1) >> 1;
+            for (int i = threadIdx.x; i < n32; i += AG_WPX_BLOCK) icc6_pairs[i] = g32[i];
+            __syncthreads();
+            icc8_words = reinterpret_cast<const uint16_t*>(icc6_pairs);
         }
     }
 
@@ -1262,6 +1293,16 @@ __global__ __launch_bounds__(AG_WPX_BLOCK) void write_px(const WriteParams p)
 #pragma unroll
                         for (int i = 0; i < PXT; ++i) s[i][k] = __float_as_uint(icc_sampled_curve(p, k, __uint_as_float(s[i][k])));
                     }
+                }
+            }
+            if constexpr (ICC == 8 && DEPTH == 32 && (PLANES == 3 || PLANES == 4)) {
+                // the stage program on every pixel of the footprint (alpha is not touched: cmsFLAGS_COPY_ALPHA)
+                const avifgpu_icc_stage32* stages = static_cast<const avifgpu_icc_stage32*>(p.icc_p8_stages);
+#pragma unroll
+                for (int i = 0; i < PXT; ++i) {
+                    const Icc8Px o = icc8_eval_pixel(stages, p.icc_p8_nstages, icc8_words,
+                                                     Icc8Px{ __uint_as_float(s[i][0]), __uint_as_float(s[i][1]), __uint_as_float(s[i][2]) });
+                    s[i][0] = __float_as_uint(o.r); s[i][1] = __float_as_uint(o.g); s[i][2] = __float_as_uint(o.b);
                 }
             }
             auto stage_row = [&](auto rescale8) {
@@ -3534,6 +3575,21 @@ static hipError_t launch_one(const WriteParams& p, hipStream_t st, char* label)
         }
     }
     if constexpr (DEPTH == 32 && PLANES >= 3) {
+        if (p.icc_p8_stages != nullptr) {           // LUT-based profile: lcms2's float stage program per pixel
+            if constexpr (!kHereIcc8) {             // those kernels live in a code object of their own (AG_WRITE_PART 38)
+                return launch_planes_d32_icc8(p, PLANES, DST16, OUT == kOutRefColor ? AVIFGPU_OUT_REFERENCE : AVIFGPU_OUT_YCBCR, XS, YS, st, label);
+            } else {
+                constexpr int PXT8 = WriteShape<DST16, PLANES, XS, 8>::PXT;
+                groups = (long long)((p.width + PXT8 - 1) / PXT8) * ((p.nrows + (1 << YS) - 1) >> YS);
+                snprintf(label, kLabelBytes, "write_px<depth=%d,planes=%d,out=%d,dst16=%d,xs=%d,ys=%d,transfer=%d,aligned=%d,icc=8>",
+                         DEPTH, PLANES, OUT, (int)DST16, XS, YS, TRANSFER, (int)aligned);
+                const size_t lds = p.icc_p8_lds_words ? (size_t)((p.icc_p8_lds_words + 1) >> 1) * 4 : 0;          // <= 48 KiB
+                if (lds) snprintf(label + strlen(label), kLabelBytes - strlen(label), " lds");
+                if (aligned) hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, true, 8>), dim3(grid_for(groups)), dim3(AG_WPX_BLOCK), lds, st, p);
+                else hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, false, 8>), dim3(grid_for(groups)), dim3(AG_WPX_BLOCK), lds, st, p);
+                return hipGetLastError();
+            }
+        }
         if (p.icc_s_tab != nullptr) {               // sampled document curves: table lookup in front of the matrix
             if constexpr (!kHereIcc6) {             // those kernels live in a code object of their own (AG_WRITE_PART 36)
                 return launch_planes_d32_icc6(p, PLANES, DST16, OUT == kOutRefColor ? AVIFGPU_OUT_REFERENCE : AVIFGPU_OUT_YCBCR, XS, YS, st, label);
@@ -3549,7 +3605,7 @@ static hipError_t launch_one(const WriteParams& p, hipStream_t st, char* label)
         }
     }
     if constexpr (!kHerePlain) {
-        return hipErrorInvalidValue;                // part 36 holds the icc = 6 launches only, the streaming part none of write_px
+        return hipErrorInvalidValue;                // parts 36 / 38 hold the icc = 6 / 8 launches only, the streaming part none of write_px
     } else {
     if constexpr (DEPTH == 32 && PLANES >= 3) {
         if (p.icc_trc_type[0] != 0) {               // ICC row transform requested: separate instantiations, the others pay nothing
@@ -3628,7 +3684,7 @@ static hipError_t launch_planes(const WriteParams& p, int planes, bool dst16, in
 {
     // 32-bit documents: gray (+ alpha) lives in part 32, RGB(A) -- the fall-back of the streaming kernels -- in part 33 (36: its icc = 6 half)
     constexpr bool gray_here = DEPTH != 32 || AG_WRITE_PART == 0 || AG_WRITE_PART == 32;
-    constexpr bool rgb_here = DEPTH != 32 || AG_WRITE_PART == 0 || AG_WRITE_PART == 33 || AG_WRITE_PART == 36;
+    constexpr bool rgb_here = DEPTH != 32 || AG_WRITE_PART == 0 || AG_WRITE_PART == 33 || AG_WRITE_PART == 36 || AG_WRITE_PART == 38;
     switch (planes) {
     case 1:  if constexpr (gray_here) return launch_planes_n<DEPTH, 1>(p, dst16, output, xs, ys, st, label); else return hipErrorInvalidValue;
     case 2:  if constexpr (gray_here) return launch_planes_n<DEPTH, 2>(p, dst16, output, xs, ys, st, label); else return hipErrorInvalidValue;
@@ -3670,6 +3726,18 @@ hipError_t launch_planes_d32_icc6(const WriteParams& p, int planes, bool dst16, 
     return hipErrorInvalidValue;                    // one object: launch_one launches the sampled-curve kernels itself
 #else
     return launch_planes<32>(p, planes, dst16, output, xs, ys, st, label);     // here launch_one compiles the icc = 6 launches only
+#endif
+}
+#endif
+
+#if AG_WRITE_PART == 0 || AG_WRITE_PART == 38
+hipError_t launch_planes_d32_icc8(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, hipStream_t st, char* label)
+{
+#if AG_WRITE_PART == 0
+    (void)p; (void)planes; (void)dst16; (void)output; (void)xs; (void)ys; (void)st; (void)label;
+    return hipErrorInvalidValue;                    // one object: launch_one launches the stage-program kernels itself
+#else
+    return launch_planes<32>(p, planes, dst16, output, xs, ys, st, label);     // here launch_one compiles the icc = 8 launches only
 #endif
 }
 #endif

@@ -336,7 +336,8 @@ int32_t avifgpu_read_rows(const avifgpu_read_desc* desc,
  * on the streaming kernels -- the matrix in single precision; the bar is on the integer codes behind the transfer curve,
  * |delta code| <= 1 and >= 99 % exact against the real lcms2, measured 99.7-100 %: tests/test_gpu_icc.py.)  Sampled `curv` tables
  * are not parametric: avifgpu_icc_prepare returns AVIFGPU_formatCannotRead for them and avifgpu_icc_prepare_sampled (below) takes
- * them; LUT-based profiles (A2B tags) are NOT covered by either and the caller keeps its lcms2 path. */
+ * them; LUT-based profiles (A2B tags) are covered by neither: the adapter captures lcms2's own stage program for them
+ * (avifgpu_icc_pipeline32 below) or keeps its lcms2 path. */
 typedef struct avifgpu_icc_transform {
     int32_t trc_type[3];         /* lcms2 parametric curve type 1..5 per channel (1 = plain gamma; gamma 1 = linear) */
     int32_t out_curve;           /* 0 = none (linear destination); 4 = inverse of lcms2 parametric type 4 (sRGB) after the matrix */
@@ -527,7 +528,7 @@ int32_t avifgpu_write_rows_icc16(const avifgpu_write_desc* desc, const avifgpu_i
  *             of the table exactly as out of byte_fn.
  * AVIFGPU_formatCannotRead (keep lcms2) if they do not: a matrix/TRC profile (lcms2 runs its matrix-shaper there -- use
  * avifgpu_icc_prepare_shaper8), another CMM, cmsFLAGS_NOOPTIMIZE.  Host-only; both callbacks run on the calling thread.
- * 32-bit documents behind such a profile stay on lcms2: its float pipeline evaluates the profile's own LUT in floating point. */
+ * 32-bit documents behind such a profile do not resample: see avifgpu_icc_pipeline32 below. */
 typedef void (*avifgpu_transform8_fn)(void* user, const uint8_t* rgb_in, uint8_t* rgb_out, uint32_t pixel_count);
 int32_t avifgpu_icc_clut8_from_transforms(avifgpu_transform_f32_fn float_fn, avifgpu_transform8_fn byte_fn, void* user,
                                           avifgpu_icc_clut16* out);
@@ -538,6 +539,69 @@ int32_t avifgpu_write_rows_icc8_table(const avifgpu_write_desc* desc, const avif
                                       const void* src, int64_t src_row_bytes,
                                       void* const dst[4], const int64_t dst_stride[4],
                                       int32_t mem_kind, void* stream);
+
+/* ---- ... and of the HDR / 32-bit save path behind a LUT-based (A2B) document profile ----------------------------------------
+ * For float formatters lcms2 does not resample (OptimizeByResampling refuses float formats): cmsDoTransform evaluates the linked,
+ * pre-optimised pipeline stage by stage in floating point, a float between stages.  avifgpu_icc_pipeline32 is that stage program,
+ * flat and pointer-free; the adapter captures it from lcms2 (integration/LcmsTableBridge.h) and each stage kind is evaluated exactly as
+ * lcms2 2.12 evaluates it on floats:
+ *   CURVES     per channel a parametric curve (lcms2 type +-1..+-5 and its parameters: EvalSegmentedFn + DefaultEvalParametricFn in
+ *              double, cast to float) or a 16-bit table of 2..4096 entries (cmsEvalToneCurveFloat with nSegments == 0: the word
+ *              _cmsQuickSaturateWord(v * 65535.0), LinLerp1D, (float)(w / 65535.0))
+ *   MATRIX     3x3 in double, the optional bias added last, cast to float (EvaluateMatrix)
+ *   CLUT16     3 in / 3 out, 2..33 grid points per input, non-uniform grids allowed; FromFloatTo16, TetrahedralInterp16 on the words,
+ *              (float)w / 65535.0f (EvaluateCLUTfloatIn16).  At most one per program.
+ *   LAB_TO_XYZ / XYZ_TO_LAB   lcms2's float PCS encodings (EvaluateLab2XYZ / EvaluateXYZ2Lab, D50)
+ * Anything else -- multi-segment curves, float CLUTs, larger grids, other stages -- has no form here: the adapter gets
+ * AVIFGPU_formatCannotRead and keeps lcms2.  A program is PROVEN before use: avifgpu_icc_pipeline32_prove evaluates the library's host
+ * restatement on a fixed probe set and requires bit-identical floats from the caller's own cmsDoTransform; only then is it stamped, and
+ * avifgpu_write_rows_icc_pipeline32 refuses an unstamped or altered program.  (The write kernel evaluates the same program -- curves and
+ * matrices in double, the words with the library's arithmetic -- tier 2 like every float path: the bar is on the integer codes behind
+ * the transfer curve.) */
+enum { AVIFGPU_ICC_PIPE_MAX_STAGES = 16, AVIFGPU_ICC_PIPE_MAX_CURVE = 4096, AVIFGPU_ICC_PIPE_MAX_GRID = 33,
+       AVIFGPU_ICC_PIPE_MAX_WORDS = 33 * 33 * 33 * 3 + 4 * 3 * 4096 };
+enum { AVIFGPU_ICC_STAGE_CURVES = 1, AVIFGPU_ICC_STAGE_MATRIX = 2, AVIFGPU_ICC_STAGE_CLUT16 = 3,
+       AVIFGPU_ICC_STAGE_LAB_TO_XYZ = 4, AVIFGPU_ICC_STAGE_XYZ_TO_LAB = 5 };
+typedef struct avifgpu_icc_stage32 {
+    int32_t kind;                /* AVIFGPU_ICC_STAGE_* */
+    int32_t curve_type[3];       /* CURVES: lcms2 parametric type +-1..+-5 per channel, 0 = 16-bit table */
+    int32_t entries[3];          /* CURVES: entries of a table channel (2..4096); CLUT16: grid points of input 0, 1, 2 (input 0 varies slowest) */
+    int32_t offset[3];           /* CURVES: first word of a table channel in words[]; CLUT16: offset[0] = first word of the grid (3 words per node) */
+    int32_t has_bias;            /* MATRIX: 1 = lcms2's stage carries an offset (added after the products) */
+    int32_t reserved;
+    double  params[3][10];       /* CURVES: parameters of a parametric channel, as lcms2 orders them */
+    double  matrix[9];           /* MATRIX: row-major, out_i = (float)(((0 + in_0 m[3i]) + in_1 m[3i+1]) + in_2 m[3i+2] [+ bias_i]) */
+    double  bias[3];
+} avifgpu_icc_stage32;
+typedef struct avifgpu_icc_pipeline32 {
+    int32_t  target;             /* AVIFGPU_ICC_TARGET_REC2020_LINEAR | AVIFGPU_ICC_TARGET_SRGB_FLOAT: the destination it was built for */
+    int32_t  stage_count;        /* 1..AVIFGPU_ICC_PIPE_MAX_STAGES */
+    int32_t  word_count;         /* words[] in use */
+    int32_t  reserved;
+    uint64_t proof;              /* stamped by avifgpu_icc_pipeline32_prove (a checksum of everything else); 0 = not proven */
+    avifgpu_icc_stage32 stages[AVIFGPU_ICC_PIPE_MAX_STAGES];
+    uint16_t words[AVIFGPU_ICC_PIPE_MAX_WORDS];      /* curve tables and the CLUT grid */
+} avifgpu_icc_pipeline32;
+
+/* Prove `pipe` against float_fn -- cmsDoTransform on the caller's TYPE_RGB_FLT transform of the same profiles, intent and flags: neutrals,
+ * the CLUT's nodes and their word neighbours, random triples in [-0.25, 4] and NaN-free extremes must come out of the library's
+ * restatement bit for bit as out of float_fn.  0 and pipe->proof stamped; AVIFGPU_formatCannotRead (keep lcms2) with the reason in
+ * avifgpu_last_error() otherwise -- a misread stage costs speed, never pixels.  Host-only; float_fn runs on the calling thread. */
+int32_t avifgpu_icc_pipeline32_prove(avifgpu_icc_pipeline32* pipe, avifgpu_transform_f32_fn float_fn, void* user);
+
+/* The library's host restatement of the program on n interleaved RGB triples (proven or not).  A DIAGNOSTIC -- the proof's engine and a
+ * test hook: no write call ever evaluates pixels on the CPU.  AVIFGPU_formatBadParameters for a malformed program. */
+int32_t avifgpu_icc_pipeline32_eval(const avifgpu_icc_pipeline32* pipe, const float* rgb_in, float* rgb_out, uint32_t n);
+
+/* avifgpu_write_rows for 32-bit RGB(A) documents with the program applied to R, G, B first (alpha copied: cmsFLAGS_COPY_ALPHA); every
+ * output the other 32-bit ICC entries take.  The target must agree with the transfer (SRGB_FLOAT: Clip).  AVIFGPU_formatBadParameters for an
+ * unstamped or altered program.  The lifetime of the program follows the contract written above avifgpu_write_rows_icc16; every call
+ * compares the device copy with the caller's program, so a program rewritten at the same address between saves is re-uploaded. */
+int32_t avifgpu_write_rows_icc_pipeline32(const avifgpu_write_desc* desc, const avifgpu_icc_pipeline32* pipe,
+                                          int32_t row0, int32_t nrows,
+                                          const void* src, int64_t src_row_bytes,
+                                          void* const dst[4], const int64_t dst_stride[4],
+                                          int32_t mem_kind, void* stream);
 
 #ifdef __cplusplus
 }

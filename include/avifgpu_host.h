@@ -166,6 +166,16 @@ avifgpu_OSErr avifgpu_host_create_heif_image_with_table(avifgpu_FormatRecord* fo
                                                         int32_t matrix_coefficients, int32_t color_primaries,
                                                         const avifgpu_icc_clut16* documentToSRGB16, avifgpu_image* img);
 
+/* The same with the stage program of a 32-bit RGB document behind a LUT-based (A2B) profile (avifgpu_icc_pipeline32, proven;
+ * integration/LcmsTableBridge.cpp builds it).  Used only at depth 32, only where the decision (explicit or LIKE_PLUGIN) says "to Rec.2020"
+ * or "to sRGB", and only where the library's own parse of the profile (avifgpu_icc_prepare, then avifgpu_icc_prepare_sampled) returns
+ * AVIFGPU_formatCannotRead -- matrix/TRC documents keep their own kernels.  AVIFGPU_formatBadParameters for a program whose target is not
+ * the decision's or that is not (or no longer) proven; NULL = the plain entry. */
+avifgpu_OSErr avifgpu_host_create_heif_image_with_pipeline(avifgpu_FormatRecord* formatRecord, int32_t alphaState,
+                                                           const avifgpu_SaveUIOptions* saveOptions, int32_t output,
+                                                           int32_t matrix_coefficients, int32_t color_primaries,
+                                                           const avifgpu_icc_pipeline32* documentPipeline, avifgpu_image* img);
+
 /*
  * Read direction: one entry for the six ReadHeifImage{Gray,RGB}{Eight,Sixteen,ThirtyTwo}Bit functions
  * (dispatch as DoReadContinue, Read.cpp:587-630; host depth from formatRecord->depth).  Sets loPlane/hiPlane/

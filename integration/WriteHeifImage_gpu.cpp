@@ -198,10 +198,25 @@ namespace
             if (got == noErr)
                 err = avifgpu_host_create_heif_image_with_table(&shim, static_cast<int32_t>(alphaState), &o, output, -1, -1, table.get(), &out);
         }
+        if (err == formatCannotRead && formatRecord->depth == 32)
+        {
+            // LUT-based (A2B) profile of a 32-bit document: lcms2 does not resample for float rows, it evaluates the linked pipeline stage by
+            // stage; LcmsTableBridge.cpp captures that program from a float transform created like InitializeForRec2020Conversion's /
+            // InitializeForSRGBConversion(..., 32)'s and the library proves it against that transform before use
+            const int32_t conversion = avifgpu_host_required_conversion_for_record(&shim, &o);
+            if (conversion == AVIFGPU_CONVERT_TO_REC2020 || conversion == AVIFGPU_CONVERT_TO_SRGB)
+            {
+                std::unique_ptr<avifgpu_icc_pipeline32> program(new avifgpu_icc_pipeline32);
+                const int32_t target = conversion == AVIFGPU_CONVERT_TO_REC2020 ? AVIFGPU_ICC_TARGET_REC2020_LINEAR : AVIFGPU_ICC_TARGET_SRGB_FLOAT;
+                if (avifgpu_lcms_document_to_pipeline32(shim.iCCprofileData, static_cast<uint32_t>(shim.iCCprofileSize), target, hasAlpha ? 1 : 0,
+                                                        program.get()) == noErr)
+                    err = avifgpu_host_create_heif_image_with_pipeline(&shim, static_cast<int32_t>(alphaState), &o, output, -1, -1, program.get(), &out);
+            }
+        }
         if (err == formatCannotRead && avifgpu_host_required_conversion_for_record(&shim, &o) > 0)
         {
-            // a profile the GPU stage does not take (LUT-based at 32 bit: lcms2 evaluates the profile's own LUT in floating point there ...): keep the
-            // reference's CPU transform, convert the rest on the GPU
+            // a profile the GPU stage does not take (a float CLUT, multi-segment curves ...): keep the reference's CPU transform, convert the
+            // rest on the GPU
             std::unique_ptr<ColorProfileConversion> converter(formatRecord->depth == 32
                 ? new ColorProfileConversion(formatRecord, hasAlpha, saveOptions.hdrTransferFunction, saveOptions.keepColorProfile)
                 : new ColorProfileConversion(formatRecord, hasAlpha, formatRecord->depth, saveOptions.keepColorProfile));
