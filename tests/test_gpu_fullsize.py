@@ -5,7 +5,8 @@ three stripes of 42 rows):
      tests/test_oracle_properties.py).  Flat launches, the 32 k-block grid cap, > 4 GiB offsets (C5's source is 4.29 GB) and every span
      index in between exist only at this size.  Integer documents: torch.equal on every plane.  Float documents (T2): max |dcode| <= 1,
      exact >= 99.95 % at 10 bit / 99.9 % at 12 bit per plane, and EVERY mismatching sample is shown to lie within 2e-5 relative of a code
-     boundary of the float64 function (for Y/Cb/Cr planes: one of the source samples the code depends on does) --
+     boundary of the float64 function (for Y/Cb/Cr planes: one of the source samples the code depends on does); beyond that, every
+     sample whose whole footprint is DETERMINED (tests/truth64.py, evaluated on the device in float64) equals the oracle exactly --
      reference lines reproduced: WriteHeifImage.cpp:1039-1135 (+ libheif's stage B where the output is Y/Cb/Cr, DESIGN.md section 3.1);
  (b) row-tile invariance: the frame converted as 8 even-row tiles (the 8-GPU sharding) is byte-identical to the one-launch frame."""
 import hashlib
@@ -14,6 +15,7 @@ import numpy as np
 import pytest
 
 import harness
+import truth64
 
 pkg = harness.pkg
 pytestmark = pytest.mark.gpu
@@ -105,16 +107,7 @@ def test_fullsize(gpu, name):
     _check_whole_frame(torch, dev, name, d, frame, whole)
 
 
-M1, M2 = np.float32(2610.0) / np.float32(16384.0), np.float32(2523.0) / np.float32(4096.0) * np.float32(128.0)
-C1 = np.float32(3424.0) / np.float32(4096.0)
-C2, C3 = np.float32(2413.0) / np.float32(4096.0) * np.float32(32.0), np.float32(2392.0) / np.float32(4096.0) * np.float32(32.0)
-
-
-def _pq64(x, peak):
-    """LinearToPQ (ColorTransfer.cpp:69-92) with the reference's float constants, evaluated in float64 (as tests/test_gpu_t2_truth.py)."""
-    x = x.astype(np.float64)
-    X = np.power(np.maximum(x, 0.0) * float(np.float32(peak) / np.float32(10000.0)), float(M1))
-    return np.where(x < 0, 0.0, np.power((float(C1) + float(C2) * X) / (1.0 + float(C3) * X), float(M2)))
+_pq64 = truth64.linear_to_pq64
 
 
 def _oracle_frame(d, host):
@@ -134,6 +127,15 @@ def _oracle_frame(d, host):
     return bufs
 
 
+def _determined_pixels(torch, d, frame, rows=512):
+    """(H, W) bool on the device: every colour sample of the pixel has a determined code (tests/truth64.py), in float64."""
+    pix = torch.empty((d.height, d.width), dtype=torch.bool, device=frame.device)
+    for r0 in range(0, d.height, rows):
+        _, m = truth64.codes_from_values(d, truth64.stage_a_values(d, frame[r0:r0 + rows]))
+        pix[r0:r0 + rows] = m.all(-1)
+    return pix
+
+
 def _check_whole_frame(torch, dev, name, d, frame, whole):
     host = frame.cpu().numpy()
     if d.depth == 16:
@@ -143,6 +145,7 @@ def _check_whole_frame(torch, dev, name, d, frame, whole):
     ssz = 2 if d.bit_depth > 8 else 1
     maxv = (1 << d.bit_depth) - 1
     color = 3 if d.planes >= 3 else 1
+    masks = truth64.output_masks(d, _determined_pixels(torch, d, frame), xp=torch) if float_tier else None
     for pl, (w, xs, ys) in harness.write_planes(d).items():
         h = (d.height + ys) >> ys
         wt = torch.from_numpy(want[pl][:h, :w]).to(dev)
@@ -158,6 +161,10 @@ def _check_whole_frame(torch, dev, name, d, frame, whole):
         print(f"{name} plane {pl}: {h}x{w} samples, exact {exact:.6f}, {bad.shape[0]} mismatches, max |dcode| {int(diff.max())}")
         assert int(diff.max()) <= 1, (name, pl)
         assert exact >= (0.9995 if d.bit_depth == 10 else 0.999), (name, pl, exact)
+        m = masks[pl][:h, :w]                         # every sample whose whole footprint is determined: exact, no rate
+        n_bad = int((gt[m] != wt[m]).sum())
+        print(f"   determined: {m.float().mean().item():.4f} of the plane, {n_bad} of them mismatching")
+        assert n_bad == 0, (name, pl, n_bad)
         if bad.shape[0] == 0:
             continue
         hi_code = torch.maximum(gt[bad[:, 0], bad[:, 1]], wt[bad[:, 0], bad[:, 1]]).cpu().numpy().astype(np.int64)   # the boundary between the two

@@ -20,41 +20,14 @@ import numpy as np
 import pytest
 
 import harness
+import truth64
 
 pkg = harness.pkg
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
-M1, M2 = f32(2610.0) / f32(16384.0), f32(2523.0) / f32(4096.0) * f32(128.0)
-C1, C2, C3 = f32(3424.0) / f32(4096.0), f32(2413.0) / f32(4096.0) * f32(32.0), f32(2392.0) / f32(4096.0) * f32(32.0)
-HA, HB, HC = f32(0.17883277), f32(0.28466892), f32(0.55991073)
-
-
-def pq_to_linear64(v, peak):                      # ColorTransfer.cpp:94-117
-    v = v.astype(np.float64)
-    e2, e1 = float(f32(1.0) / M2), float(f32(1.0) / M1)
-    mult = float(f32(10000.0) / f32(peak))
-    x = np.power(v, e2)
-    t = np.maximum(x - float(C1), 0.0) / (float(C2) - float(C3) * x)
-    return np.where(v < 0, 0.0, np.power(t, e1) * mult)
-
-
-def hlg_to_linear64(v):                           # :166-190
-    v = v.astype(np.float64)
-    hi = (np.exp((v - float(HC)) / float(HA)) + float(HB)) / 12.0
-    lo = v * v * float(f32(1.0) / f32(3.0))
-    return np.where(v > 0.5, hi, lo)
-
-
-def smpte428_to_linear64(v):                      # :129-139
-    return np.power(v.astype(np.float64), float(f32(2.6))) * float(f32(52.37) / f32(48.0))
-
-
-def linear_to_pq64(x, peak):                      # :69-92
-    x = x.astype(np.float64)
-    mult = float(f32(peak) / f32(10000.0))
-    X = np.power(np.maximum(x, 0.0) * mult, float(M1))
-    return np.where(x < 0, 0.0, np.power((float(C1) + float(C2) * X) / (1.0 + float(C3) * X), float(M2)))
+pq_to_linear64, hlg_to_linear64, smpte428_to_linear64 = truth64.pq_to_linear64, truth64.hlg_to_linear64, truth64.smpte428_to_linear64
+linear_to_pq64 = truth64.linear_to_pq64
 
 
 @pytest.mark.parametrize("bits", [10, 12])
