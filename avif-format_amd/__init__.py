@@ -153,6 +153,12 @@ def icc_pipeline32_from_profile(profile_bytes: bytes, target=ICC_TARGET_REC2020_
     return rc, t
 
 
+class ContentLightLevel(ctypes.Structure):
+    """avifgpu_content_light_level: the clli fields and what they were rounded from."""
+    _fields_ = [("max_cll", ctypes.c_uint16), ("max_fall", ctypes.c_uint16), ("max_code", c_int32), ("pixels", ctypes.c_uint64),
+                ("max_cll_nits", ctypes.c_double), ("max_fall_nits", ctypes.c_double)]
+
+
 class DeviceInfo(ctypes.Structure):
     _fields_ = [("device", c_int32), ("numa_node", c_int32), ("workers", c_int32), ("workers_pinned", c_int32),
                 ("pci_bus_id", ctypes.c_char * 32), ("cpulist", ctypes.c_char * 256)]
@@ -219,6 +225,9 @@ ABI = [
     ("avifgpu_probe_pattern_read", c_int32, [POINTER(ReadDesc), c_int32, c_int32, POINTER(_PLANES4), POINTER(_STRIDES4), c_void_p, c_int64, c_void_p]),
     ("avifgpu_probe_set_shape", None, [c_int32, c_int32, c_int32]),
     ("avifgpu_probe_pattern_rgb32_444", c_int32, [c_void_p, c_int64, POINTER(c_void_p * 3), POINTER(c_int64 * 3), c_int32, c_int32, c_void_p]),
+    ("avifgpu_histogram_attach", c_int32, [c_void_p, c_int32, c_int32]),
+    ("avifgpu_light_level_from_histogram", c_int32, [c_void_p, c_int32, c_int32, ctypes.c_double, POINTER(ContentLightLevel)]),
+    ("avifgpu_probe_histogram", c_int32, [POINTER(WriteDesc), c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
 ]
 
 
@@ -228,7 +237,9 @@ ABI = [
 ABI4_NEW = frozenset(("avifgpu_probe_pattern_read", "avifgpu_probe_pattern_rgb32_444", "avifgpu_device_traffic_get", "avifgpu_device_traffic_reset",
                       "avifgpu_topology_plan", "avifgpu_icc_prepare_sampled", "avifgpu_write_rows_icc_sampled",
                       "avifgpu_icc_clut16_from_transforms",
-                      "avifgpu_icc_clut8_from_transforms", "avifgpu_write_rows_icc8_table", "avifgpu_probe_set_shape"))       # (ABI 5, round 6)
+                      "avifgpu_icc_clut8_from_transforms", "avifgpu_write_rows_icc8_table", "avifgpu_probe_set_shape",        # (ABI 5, round 6)
+                      "avifgpu_histogram_attach", "avifgpu_light_level_from_histogram", "avifgpu_probe_histogram",
+                      "avifgpu_host_save_wants_light_level"))   # (the code histogram)
 
 
 def bind(lib: ctypes.CDLL, table=ABI) -> ctypes.CDLL:
@@ -415,6 +426,55 @@ class AvifGpu:
 
     def read_algorithmic_bytes(self, desc: ReadDesc, nrows: int) -> int:
         return self.lib.avifgpu_read_algorithmic_bytes(ctypes.byref(desc), nrows)
+
+
+class code_histogram:
+    """Arm the calling thread's code histogram for the `with` block, disarm it on the way out (avifgpu_histogram_attach).
+
+    `bins` holds 1 << bit_depth 64-bit counters and is never zeroed by the library: a numpy uint64 array (mem = MEM_HOST), a
+    contiguous torch int64 / uint64 tensor on the device the calls run on (mem = MEM_DEVICE), or a raw address."""
+
+    def __init__(self, bins, bit_depth: int, mem=MEM_HOST):
+        self.bins, self.bit_depth, self.mem = bins, int(bit_depth), mem
+
+    def _address(self):
+        b = self.bins
+        if hasattr(b, "data_ptr"):
+            n, ptr = b.numel(), b.data_ptr()
+            if b.element_size() != 8 or not b.is_contiguous():
+                raise ValueError("code_histogram: bins must be contiguous 64-bit counters")
+        elif hasattr(b, "ctypes"):
+            n, ptr = b.size, b.ctypes.data
+            if b.dtype.itemsize != 8 or not b.flags["C_CONTIGUOUS"]:
+                raise ValueError("code_histogram: bins must be contiguous 64-bit counters")
+        else:
+            return int(b)
+        if n < (1 << self.bit_depth):
+            raise ValueError("code_histogram: %d bins for %d-bit codes" % (n, self.bit_depth))
+        return ptr
+
+    def __enter__(self):
+        lib = load()
+        code = lib.avifgpu_histogram_attach(self._address(), self.bit_depth, self.mem)
+        if code != 0:
+            raise AvifGpuError(code, lib.avifgpu_last_error().decode())
+        return self
+
+    def __exit__(self, *exc):
+        load().avifgpu_histogram_attach(None, 0, MEM_HOST)
+        return False
+
+
+def light_level_from_histogram(bins, bit_depth: int, transfer=TRANSFER_PQ, percentile: float = 1.0) -> ContentLightLevel:
+    """MaxCLL / MaxFALL of a host histogram (numpy uint64 array of 1 << bit_depth bins): avifgpu_light_level_from_histogram."""
+    lib = load()
+    out = ContentLightLevel()
+    if bins is not None and (bins.dtype.itemsize != 8 or not bins.flags["C_CONTIGUOUS"] or (bit_depth in (10, 12) and bins.size < (1 << bit_depth))):
+        raise ValueError("light_level_from_histogram: bins must be 1 << bit_depth contiguous 64-bit counters")
+    code = lib.avifgpu_light_level_from_histogram(bins.ctypes.data if bins is not None else None, bit_depth, transfer, percentile, ctypes.byref(out))
+    if code != 0:
+        raise AvifGpuError(code, lib.avifgpu_last_error().decode())
+    return out
 
 
 def yuv_coefficients(has_nclx: int, matrix: int, primaries: int):

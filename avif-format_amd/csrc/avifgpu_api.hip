@@ -29,6 +29,9 @@ namespace {
 thread_local char g_err[512] = "";
 thread_local char g_kernel[kLabelBytes] = "";
 int g_hot_variant = kHotDefault;
+// the calling thread's code histogram (avifgpu_histogram_attach): host-only bookkeeping, survives a re-binding of the devices
+thread_local uint64_t* g_hist_bins = nullptr;
+thread_local int g_hist_bits = 0, g_hist_kind = AVIFGPU_MEM_HOST;
 }
 
 namespace avifgpu {
@@ -50,6 +53,24 @@ void set_error(const char* msg) { snprintf(g_err, sizeof(g_err), "%s", msg); }
 const char* last_error() { return g_err; }
 void set_last_kernel(const char* label) { snprintf(g_kernel, sizeof(g_kernel), "%s", label); }
 int hot_variant() { return g_hot_variant; }
+
+int histogram_for_call(const avifgpu_write_desc* d, int mem_kind, uint64_t** bins)
+{
+    *bins = nullptr;
+    if (!g_hist_bins || d->depth != 32) return 0;
+    if (d->bit_depth != g_hist_bits)
+        return fail(AVIFGPU_formatBadParameters, "the armed code histogram has %d-bit bins, this call writes %d-bit codes", g_hist_bits, d->bit_depth);
+    if (mem_kind != g_hist_kind)
+        return fail(AVIFGPU_formatBadParameters, "the armed code histogram lives in %s memory, this call's pointers do not",
+                    g_hist_kind == AVIFGPU_MEM_DEVICE ? "device" : "host");
+    *bins = g_hist_bins;
+    return 0;
+}
+uint64_t* histogram_host_bins(int* nbins)
+{
+    *nbins = g_hist_bins ? 1 << g_hist_bits : 0;
+    return g_hist_kind == AVIFGPU_MEM_HOST ? g_hist_bins : nullptr;
+}
 
 } // namespace avifgpu
 
@@ -777,6 +798,8 @@ int write_rows_any(const avifgpu_write_desc* d, const IccArgs& icc, int32_t row0
     if (err) return err;
     if ((err = check_write_buffers(d, g, nrows, src, src_row_bytes, dst, dst_stride))) return err;
     if (context_count() == 0) return fail(AVIFGPU_formatBadParameters, "%s", kNoDevice);
+    uint64_t* hist = nullptr;
+    if ((err = histogram_for_call(d, mem_kind, &hist))) return err;            // before anything is launched
     if (nrows == 0) return 0;
     if (icc.c16 || icc.s32 || icc.c8t) icc_epoch_for_call(row0, nrows);       // the device copies of these tables are re-verified once per device and epoch
 
@@ -789,6 +812,10 @@ int write_rows_any(const avifgpu_write_desc* d, const IccArgs& icc, int32_t row0
         for (int pl = 0; pl < 4; ++pl) { p.dst[pl] = (uint8_t*)dst[pl]; p.dst_stride[pl] = dst_stride[pl]; }
         const hipError_t e = launch_write(p, d->depth, d->planes, g.dst16, d->output, g.xs, g.ys, g_hot_variant, st, g_kernel);
         if (e != hipSuccess) return hip_fail(e, "kernel launch", AVIFGPU_writErr);
+        if (hist) {                                     // the statistics kernel behind it on the caller's stream, straight into the caller's device bins
+            const hipError_t eh = launch_write_hist(p, d->planes, reinterpret_cast<unsigned long long*>(hist), st);
+            if (eh != hipSuccess) return hip_fail(eh, "histogram kernel launch", AVIFGPU_writErr);
+        }
         return 0;
     }
     if (mem_kind != AVIFGPU_MEM_HOST) return fail(AVIFGPU_formatBadParameters, "bad mem_kind %d", mem_kind);
@@ -915,6 +942,80 @@ int64_t avifgpu_read_algorithmic_bytes(const avifgpu_read_desc* d, int32_t nrows
         total += rows * rb;
     }
     return total;
+}
+
+int32_t avifgpu_histogram_attach(uint64_t* bins, int32_t bit_depth, int32_t mem_kind)
+{
+    g_err[0] = 0;
+    if (!bins) { g_hist_bins = nullptr; g_hist_bits = 0; g_hist_kind = AVIFGPU_MEM_HOST; return 0; }
+    if (bit_depth != 10 && bit_depth != 12)
+        return fail(AVIFGPU_formatBadParameters, "avifgpu_histogram_attach: bit depth %d (a 32-bit document is saved at 10 or 12 bit)", bit_depth);
+    if (mem_kind != AVIFGPU_MEM_HOST && mem_kind != AVIFGPU_MEM_DEVICE)
+        return fail(AVIFGPU_formatBadParameters, "avifgpu_histogram_attach: bad mem_kind %d", mem_kind);
+    g_hist_bins = bins; g_hist_bits = bit_depth; g_hist_kind = mem_kind;
+    return 0;
+}
+
+// SMPTE ST 2084 EOTF, exact rational constants, double: code value in [0, 1] -> cd/m2
+static double pq_eotf_nits(double e)
+{
+    const double m1 = 2610.0 / 16384.0, m2 = 2523.0 / 4096.0 * 128.0;
+    const double c1 = 3424.0 / 4096.0, c2 = 2413.0 / 4096.0 * 32.0, c3 = 2392.0 / 4096.0 * 32.0;
+    const double ep = pow(e, 1.0 / m2);
+    const double num = ep - c1 > 0.0 ? ep - c1 : 0.0;
+    return 10000.0 * pow(num / (c2 - c3 * ep), 1.0 / m1);
+}
+
+int32_t avifgpu_light_level_from_histogram(const uint64_t* bins, int32_t bit_depth, int32_t transfer, double percentile,
+                                           avifgpu_content_light_level* out)
+{
+    g_err[0] = 0;
+    if (!bins || !out) return fail(AVIFGPU_formatBadParameters, "avifgpu_light_level_from_histogram: null argument");
+    if (bit_depth != 10 && bit_depth != 12) return fail(AVIFGPU_formatBadParameters, "avifgpu_light_level_from_histogram: bit depth %d is not 10 or 12", bit_depth);
+    if (transfer != AVIFGPU_TRANSFER_PQ)
+        return fail(AVIFGPU_formatBadParameters, "avifgpu_light_level_from_histogram: transfer %d: only PQ codes are absolute luminance", transfer);
+    if (!(percentile > 0.0 && percentile <= 1.0)) return fail(AVIFGPU_formatBadParameters, "avifgpu_light_level_from_histogram: percentile outside (0, 1]");
+    const int nbins = 1 << bit_depth;
+    uint64_t n = 0;
+    for (int c = 0; c < nbins; ++c) n += bins[c];
+    if (n == 0) return fail(AVIFGPU_formatBadParameters, "avifgpu_light_level_from_histogram: the histogram is empty");
+    const double need = ceil(percentile * (double)n);
+    const double maxv = (double)(nbins - 1);
+    uint64_t cum = 0;
+    int cp = -1;
+    double sum = 0.0;
+    for (int c = 0; c < nbins; ++c) {                       // ascending code order
+        if (!bins[c]) continue;
+        cum += bins[c];
+        if (cp < 0 && (double)cum >= need) cp = c;
+        sum += (double)bins[c] * pq_eotf_nits((double)c / maxv);
+    }
+    if (cp < 0) { for (int c = nbins - 1; c >= 0; --c) if (bins[c]) { cp = c; break; } }     // ceil(p n) rounded past n in double: the highest non-empty bin
+    out->max_code = cp;
+    out->pixels = n;
+    out->max_cll_nits = pq_eotf_nits((double)cp / maxv);
+    out->max_fall_nits = sum / (double)n;
+    const double a = floor(out->max_cll_nits + 0.5), b = floor(out->max_fall_nits + 0.5);
+    out->max_cll = (uint16_t)(a > 65535.0 ? 65535.0 : a);
+    out->max_fall = (uint16_t)(b > 65535.0 ? 65535.0 : b);
+    return 0;
+}
+
+int32_t avifgpu_probe_histogram(const avifgpu_write_desc* d, int32_t twin, const void* src, int64_t src_row_bytes, uint64_t* bins, void* stream)
+{
+    g_err[0] = 0;
+    WriteGeom g;
+    int err = check_write(d, 0, d ? d->height : 0, g);
+    if (err) return err;
+    if (d->depth != 32 || !src || !bins || twin < 0 || twin > 2 || src_row_bytes < (int64_t)d->width * d->planes * 4)
+        return fail(AVIFGPU_formatBadParameters, "avifgpu_probe_histogram: a depth-32 descriptor, device pointers and twin 0..2");
+    if (context_count() == 0) return fail(AVIFGPU_formatBadParameters, "%s", kNoDevice);
+    WriteParams p;
+    if ((err = fill_write_params(d, 0, d->height, g, IccArgs(), p))) return err;
+    p.src = (const uint8_t*)src; p.src_row_bytes = src_row_bytes;
+    const hipError_t e = launch_write_hist(p, d->planes, reinterpret_cast<unsigned long long*>(bins), (hipStream_t)stream, twin);
+    if (e != hipSuccess) return hip_fail(e, "avifgpu_probe_histogram (the twins take aligned RGB rows, PQ, no profile)", AVIFGPU_formatBadParameters);
+    return 0;
 }
 
 int32_t avifgpu_write_rows(const avifgpu_write_desc* d, int32_t row0, int32_t nrows,

@@ -40,8 +40,9 @@ struct Args {
     int width = 0, height = 0, depth = 8, planes = 3, bits = 8, transfer = AVIFGPU_TRANSFER_CLIP, peak = 1000;
     int alpha = AVIFGPU_ALPHA_NONE, output = AVIFGPU_OUT_REFERENCE, chroma = AVIFGPU_CHROMA_444;
     int matrix = AVIFGPU_MATRIX_BT601, primaries = AVIFGPU_PRIMARIES_BT709, tc = 2, limited = 0, colorspace = AVIFGPU_COLORSPACE_YCBCR;
-    int lossless = 0, maxdata = 0, device = 0, hlg_ootf = 0, nclx = 0, keep_profile = 0;
+    int lossless = 0, maxdata = 0, device = 0, hlg_ootf = 0, nclx = 0, keep_profile = 0, light_level = 0;
     float gamma = 1.2f;
+    double percentile = 1.0;
 };
 
 [[noreturn]] void usage(const char* why)
@@ -50,7 +51,8 @@ struct Args {
     fprintf(stderr,
         "usage: avifgpu_cli write --width W --height H --depth 8|16|32 --planes 1..4 --bits 8|10|12 [--transfer clip|pq|smpte428]\n"
         "                         [--peak NITS] [--alpha none|straight|premultiplied] [--ycbcr 444|422|420] [--matrix N] [--primaries N]\n"
-        "                         [--lossless] [--icc PROFILE [--keep-profile]] [--maxdata BYTES] [--device N] IN.raw OUT.planes\n"
+        "                         [--lossless] [--icc PROFILE [--keep-profile]] [--maxdata BYTES] [--device N]\n"
+        "                         [--light-level [--percentile P]] IN.raw OUT.planes\n"
         "       avifgpu_cli read  --width W --height H --depth 8|16|32 --bits 8|10|12 --colorspace ycbcr|rgb|mono [--chroma 444|422|420]\n"
         "                         [--alpha none|straight|premultiplied] [--matrix N --primaries N --tc N [--limited]] [--peak NITS]\n"
         "                         [--hlg-ootf --gamma G] [--maxdata BYTES] [--device N] IN.planes OUT.raw\n");
@@ -89,6 +91,8 @@ Args parse(int argc, char** argv)
         else if (o == "--hlg-ootf") a.hlg_ootf = 1;
         else if (o == "--lossless") a.lossless = 1;
         else if (o == "--keep-profile") a.keep_profile = 1;
+        else if (o == "--light-level") a.light_level = 1;
+        else if (o == "--percentile") a.percentile = atof(val());
         else if (o == "--icc") a.icc = val();
         else if (o == "--transfer") a.transfer = pick(val(), {{"clip", AVIFGPU_TRANSFER_CLIP}, {"pq", AVIFGPU_TRANSFER_PQ}, {"smpte428", AVIFGPU_TRANSFER_SMPTE428}}, "--transfer");
         else if (o == "--alpha") a.alpha = pick(val(), {{"none", AVIFGPU_ALPHA_NONE}, {"straight", AVIFGPU_ALPHA_STRAIGHT}, {"premultiplied", AVIFGPU_ALPHA_PREMULTIPLIED}}, "--alpha");
@@ -172,11 +176,30 @@ int do_write(const Args& a)
         fprintf(stderr, "icc: %s\n", conversion == AVIFGPU_CONVERT_TO_REC2020 ? "convert to Rec.2020"
                                     : conversion == AVIFGPU_CONVERT_TO_SRGB ? "convert to sRGB" : "no conversion");
     }
+    // --light-level: the code histogram of the save, armed around the shim's call on this thread (all tiles summed), then MaxCLL / MaxFALL
+    std::vector<uint64_t> bins;
+    if (a.light_level) {
+        if (avifgpu_host_save_wants_light_level(&g_host.fr, &o) != 1) {
+            fprintf(stderr, "avifgpu_cli: --light-level applies to 32-bit PQ saves only\n");
+            return 1;
+        }
+        bins.assign((size_t)1 << (a.bits == 12 ? 12 : 10), 0);
+        const int hrc = avifgpu_histogram_attach(bins.data(), a.bits, AVIFGPU_MEM_HOST);
+        if (hrc) return fail("avifgpu_histogram_attach", hrc);
+    }
     avifgpu_image img{};
     const int rc = avifgpu_host_create_heif_image(&g_host.fr, a.alpha, &o, a.output, a.lossless ? AVIFGPU_MATRIX_RGB_GBR : a.matrix,
                                                   a.primaries, &img);
     fclose(g_host.file);
+    if (a.light_level) (void)avifgpu_histogram_attach(nullptr, 0, AVIFGPU_MEM_HOST);
     if (rc) return fail("avifgpu_host_create_heif_image", rc);
+    if (a.light_level) {
+        avifgpu_content_light_level ll{};
+        const int lrc = avifgpu_light_level_from_histogram(bins.data(), a.bits, o.hdrTransferFunction, a.percentile, &ll);
+        if (lrc) { avifgpu_image_free(&img); return fail("avifgpu_light_level_from_histogram", lrc); }
+        fprintf(stderr, "light-level: MaxCLL %u MaxFALL %u code %d pixels %llu\n", (unsigned)ll.max_cll, (unsigned)ll.max_fall, (int)ll.max_code,
+                (unsigned long long)ll.pixels);
+    }
     FILE* out = fopen(a.out.c_str(), "wb");
     if (!out) { perror(a.out.c_str()); return 1; }
     size_t total = 0;

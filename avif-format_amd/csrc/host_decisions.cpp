@@ -79,6 +79,15 @@ avifgpu_OSErr avifgpu_host_normalize_save_options(const avifgpu_FormatRecord* fo
     return AVIFGPU_noErr;
 }
 
+int32_t avifgpu_host_save_wants_light_level(const avifgpu_FormatRecord* formatRecord, const avifgpu_SaveUIOptions* saveOptions)
+{
+    if (!formatRecord || !saveOptions) return AVIFGPU_formatBadParameters;
+    if (formatRecord->depth != 32) return 0;                       // no clli for SDR documents
+    avifgpu_SaveUIOptions o = *saveOptions;                        // the transfer DoWriteStart would save with (32-bit mono -> Clip)
+    if (avifgpu_host_normalize_save_options(formatRecord, &o) != AVIFGPU_noErr) return AVIFGPU_formatBadParameters;
+    return o.hdrTransferFunction == AVIFGPU_TRANSFER_PQ ? 1 : 0;   // only PQ codes are absolute luminance
+}
+
 int32_t avifgpu_host_alpha_state(const avifgpu_FormatRecord* formatRecord, const avifgpu_SaveUIOptions* saveOptions)
 {
     if (!formatRecord || !saveOptions) return AVIFGPU_formatBadParameters;

@@ -111,6 +111,12 @@ struct WriteParams {
     int32_t icc_p8_lds_words;     // words[] copied to LDS per workgroup (the program's tables fit 48 KiB); 0 = read from device memory
 };
 
+// The code histogram of a 32-bit save (write_hist_px, write_kernels.hip): 64-bit counters in device memory, added to with vector atomics
+struct HistParams {
+    unsigned long long* bins;    // [nbins]
+    int32_t nbins;               // 1 << bit_depth: 1024 | 4096
+};
+
 struct ReadParams {
     const uint8_t* src[4];       // Y,Cb,Cr,A / R,G,B,A / Y,-,-,A at row row0 (chroma: row0 >> ys)
     int64_t        src_stride[4];

@@ -61,6 +61,7 @@ struct Job {
     const void* planes_in[4] = {};   int64_t planes_in_stride[4] = {}; // read
     void* rows_out = nullptr;        int64_t rows_out_stride = 0;
     IccArgs icc;
+    bool hist = false;                                     // write, depth 32: the calling thread had a code histogram armed (enqueue side decides, the worker counts)
     // filled by start(): what finish() still has to copy out of the pinned bounce buffer
     struct Bounce { uint8_t* dst; int64_t dst_stride; size_t off, pitch, bytes; int rows; } bounce[4];
     int nbounce = 0;
@@ -99,7 +100,12 @@ struct Ctx {
     // what this context moved over its device's link since the binding (or the last avifgpu_device_traffic_reset): payload bytes of the
     // tiles it issued, per direction, and how many of them went through a bounce buffer (pageable caller memory)
     std::atomic<uint64_t> tiles{0}, bytes_h2d{0}, bytes_d2h{0}, bytes_bounced{0};
+    // code histogram of the tiles this context converted for an armed caller (avifgpu_histogram_attach): kHistBins 64-bit counters on the
+    // device, allocated and zeroed by the worker on first use, freed when it exits; wait_all() adds them to the caller's bins and zeroes them
+    unsigned long long* d_hist = nullptr;
+    std::atomic<bool> hist_dirty{false};
 };
+constexpr int kHistBins = 4096;
 
 // Where a bound device sits in the host: PCI bus id, NUMA node, the node's CPUs ("report which GPUs hang off which
 // root complex").  Read once per binding from sysfs; AVIFGPU_SYSFS_ROOT redirects the reads (tests use a fake tree).
@@ -480,7 +486,6 @@ int start_write(Ctx& c, Job& j)
     }
     e = launch_write(p, d->depth, d->planes, g.dst16, d->output, g.xs, g.ys, hot_variant(), st, j.label);
     if (e != hipSuccess) { (void)hipStreamSynchronize(st); return hip_fail(e, "kernel launch", AVIFGPU_writErr); }
-
     // planes back: straight into page-locked destinations, through the pinned bounce buffer otherwise
     j.nbounce = 0;
     bool any_pageable = false;
@@ -504,6 +509,21 @@ int start_write(Ctx& c, Job& j)
         if (e != hipSuccess) { (void)hipStreamSynchronize(st); return hip_fail(e, "D2H copy", AVIFGPU_writErr); }
         c.bytes_d2h.fetch_add((uint64_t)pbytes[pl] * (uint64_t)prow[pl], std::memory_order_relaxed);
         if (!pinned_dst[pl]) c.bytes_bounced.fetch_add((uint64_t)pbytes[pl] * (uint64_t)prow[pl], std::memory_order_relaxed);
+    }
+    if (j.hist) {
+        // the statistics kernel on the tile that is already resident (no second upload), on the slot's stream BEHIND the planes' copies back: it
+        // reads d_in only, so the planes leave as early as they do unarmed (the slot is held until the event behind it either way)
+        if (!c.d_hist) {
+            void* hb = nullptr;
+            e = hipMalloc(&hb, kHistBins * sizeof(unsigned long long));
+            if (e == hipSuccess) e = hipMemsetAsync(hb, 0, kHistBins * sizeof(unsigned long long), st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);          // once per context: the other slots' streams count into it too
+            if (e != hipSuccess) { if (hb) (void)hipFree(hb); (void)hipStreamSynchronize(st); return hip_fail(e, "hipMalloc(histogram)", AVIFGPU_memFullErr); }
+            c.d_hist = static_cast<unsigned long long*>(hb);
+        }
+        c.hist_dirty.store(true, std::memory_order_release);
+        e = launch_write_hist(p, d->planes, c.d_hist, st);
+        if (e != hipSuccess) { (void)hipStreamSynchronize(st); return hip_fail(e, "histogram kernel launch", AVIFGPU_writErr); }
     }
     if ((e = hipEventRecord(sl.done, st)) != hipSuccess) { (void)hipStreamSynchronize(st); return hip_fail(e, "event record", AVIFGPU_writErr); }
     return 0;
@@ -707,6 +727,7 @@ void worker_main(Ctx* cp)
         if (sl.stream) (void)hipStreamDestroy(sl.stream);
         sl = Slot();
     }
+    if (c.d_hist) { (void)hipFree(c.d_hist); c.d_hist = nullptr; }
 }
 
 Ctx* ctx_at(int i)
@@ -951,6 +972,9 @@ int write_tile_enqueue(int ctx, int slot, const avifgpu_write_desc* d, int row0,
     j.rows_in = src; j.rows_in_stride = src_row_bytes;
     for (int pl = 0; pl < 4; ++pl) { j.planes_out[pl] = dst[pl]; j.planes_out_stride[pl] = dst_stride[pl]; }
     j.icc = icc;
+    uint64_t* hist = nullptr;                              // the arming is the calling thread's; a mismatch fails here, before anything is queued
+    if ((err = histogram_for_call(d, AVIFGPU_MEM_HOST, &hist))) return err;
+    j.hist = hist != nullptr;
     return enqueue(ctx, j);
 }
 
@@ -980,7 +1004,37 @@ int wait_slot(int ctx, int slot)
     return 0;
 }
 
-int wait_all()
+namespace {
+// The contexts are idle: add what their tiles counted to the calling thread's armed bins (discard: only zero them), device by device on
+// the calling thread.  The caller's current device is put back.
+int collect_histograms(bool discard)
+{
+    uint64_t* bins = nullptr;
+    int nbins = 0;
+    if (!discard) bins = histogram_host_bins(&nbins);
+    int cur = -1, rc = 0;
+    std::vector<unsigned long long> tmp;
+    for (int i = 0; i < context_count(); ++i) {
+        Ctx* c = ctx_at(i);
+        if (!c->d_hist || !c->hist_dirty.load(std::memory_order_acquire)) continue;
+        if (cur == -1 && hipGetDevice(&cur) != hipSuccess) { (void)hipGetLastError(); cur = -2; }
+        tmp.resize(kHistBins);
+        hipError_t e = hipSetDevice(c->device);
+        if (e == hipSuccess) e = hipMemcpy(tmp.data(), c->d_hist, kHistBins * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemsetAsync(c->d_hist, 0, kHistBins * sizeof(unsigned long long), nullptr);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);        // the slots' streams do not wait for the default stream
+        if (e != hipSuccess) { if (!rc) rc = hip_fail(e, "histogram read-back", AVIFGPU_writErr); continue; }
+        c->hist_dirty.store(false, std::memory_order_release);
+        if (bins) for (int k = 0; k < nbins; ++k) bins[k] += tmp[k];
+    }
+    if (cur >= 0) (void)hipSetDevice(cur);
+    return rc;
+}
+int wait_all_impl(bool discard_hist);
+}
+int wait_all() { return wait_all_impl(false); }
+namespace {
+int wait_all_impl(bool discard_hist)
 {
     int first = 0;
     char msg[512] = "";
@@ -996,8 +1050,10 @@ int wait_all()
         if (c->err && !first) { first = c->err; snprintf(msg, sizeof(msg), "%s", c->err_msg); }
         c->err = 0; c->err_msg[0] = 0;
     }
+    const int hrc = collect_histograms(discard_hist || first != 0);
     if (first) set_error(msg);
-    return first;
+    return first ? first : hrc;
+}
 }
 
 // ---- whole-range host conversions ---------------------------------------------------------------------------------------
@@ -1061,7 +1117,7 @@ int write_rows_host(const avifgpu_write_desc* d, int row0, int nrows, const void
         }
         if (!any) break;
     }
-    const int werr = wait_all();                          // drains everything, also after a failure
+    const int werr = wait_all_impl(err != 0);             // drains everything, also after a failure (which counts nothing)
     return err ? err : werr;
 }
 

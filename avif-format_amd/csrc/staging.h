@@ -52,10 +52,16 @@ void read_plane_extent(const avifgpu_read_desc* d, const ReadGeom& g, int plane,
 bool read_plane_used(const avifgpu_read_desc* d, const ReadGeom& g, int plane);
 
 int  hot_variant();
+// The calling thread's armed code histogram (avifgpu_histogram_attach): for a depth-32 write of `mem_kind`, 0 and *bins = the armed
+// counters (nullptr: nothing armed, or the descriptor is not counted), or formatBadParameters with a message when bit depth or memory kind disagree.
+int  histogram_for_call(const avifgpu_write_desc* d, int mem_kind, uint64_t** bins);
+uint64_t* histogram_host_bins(int* nbins);           // the calling thread's armed HOST counters, or nullptr
 
 // ---- write_kernels.hip / read_kernels.hip ---------------------------------------------------------------------------
 hipError_t launch_write(const WriteParams& p, int depth, int planes, bool dst16, int output, int xs, int ys,
                         int variant, hipStream_t st, char* label);
+// the code histogram of the same tile (depth 32), enqueued behind launch_write(): bins = 1 << bit_depth counters on the stream's device
+hipError_t launch_write_hist(const WriteParams& p, int planes, unsigned long long* bins, hipStream_t st, int twin = 0);   // twin: avifgpu_probe_histogram
 hipError_t launch_read(const ReadParams& p, int colorspace, int depth, bool alpha, int xs, int ys,
                        hipStream_t st, char* label);
 void release_device_caches();                        // read tables + ICC tables of every device (avifgpu_shutdown)
@@ -91,7 +97,8 @@ int  write_tile_enqueue(int ctx, int slot, const avifgpu_write_desc* d, int row0
 int  read_tile_enqueue(int ctx, int slot, const avifgpu_read_desc* d, int row0, int nrows, const void* const src[4],
                        const int64_t src_stride[4], void* dst, int64_t dst_row_bytes);
 int  wait_slot(int ctx, int slot);                   // the tile last queued on (ctx, slot) has fully landed in host memory
-int  wait_all();                                     // every context idle; returns the first error any tile produced
+int  wait_all();                                     // every context idle; returns the first error any tile produced.  Tiles that counted into their
+                                                     // contexts' code histograms: the sums are added to `hist_bins` of the calling thread (nothing on an error)
 // One host-pointer conversion (whole-range call or a shim save / open) at a time per process: they share slots and error state.
 void host_call_lock();
 void host_call_unlock();

@@ -43,6 +43,7 @@ namespace avifgpu {
 //    32  write_px for gray (+ alpha) f32 documents (the fall-back of their streaming kernels), 33 for RGB(A) f32 documents (the fall-back of the streaming kernels
 //        and the parametric-curve ICC variants), 36 write_px<32, ..., icc = 6>: documents whose profile carries sampled curves, 38 write_px<32, ..., icc = 8>:
 //        documents behind a LUT-based profile (lcms2's float stage program)
+//    40  write_hist_px, the code histogram of a 32-bit save (launch_write_hist; loaded only by a process that arms one)
 //    0   everything in one object (tools/ab_variants.sh builds its A/B libraries that way).
 // A kernel is emitted where a launch of it is instantiated; the launchers of a part are compiled in that part only (kHere* below), the
 // streaming part reaches the others through the four launch_planes_* functions.
@@ -917,6 +918,8 @@ __global__ __launch_bounds__(AG_WPX_BLOCK) void write_px(const WriteParams p)
         icc7_pos = icc7_tab;
     }
 
+    // (the ICC set-up from here to icc_regs_load_f, the icc = 6 / 8 blocks in front of stage_a below and launch_one's choice of ICC are
+    // repeated in write_hist_px / launch_hist_icc, which must count the codes this kernel writes: keep the two in step)
     // sampled-curve ICC variant: the profile's tables as (T[i], T[i+1]) pairs in dynamic LDS (4 bytes per entry, sized by the launch)
     extern __shared__ uint32_t icc6_pairs[];
     const bool icc6_lds = ICC == 6 && p.icc_s_lds != 0;
@@ -4081,6 +4084,293 @@ hipError_t launch_stream_f32_sub_rgba(const WriteParams& p, int depth, int plane
     return hipSuccess;
 }
 #endif
+
+// ---- code histogram of a 32-bit save (content light level) -- code object 40 ----------------------------------------
+// count[max(code R, code G, code B)] += 1 per pixel (gray: code Y) of the codes stage A produces -- stage_a<32, ...> itself, behind the same
+// ICC stage write_px runs, with the same WriteParams -- and no pixel stored.  Three curve evaluations per colour pixel: the fast curves
+// are not proven monotone on floats, so max(code) is not taken as code(max).
+//   work    : the generic kernel's mapping -- a lane owns 4 adjacent pixels of a row (48 / 64 / 16 / 32 bytes as non-temporal 16-byte
+//             loads), a wave 256 pixels; a persistent grid of at most kHistMaxBlocks workgroups of 16 waves walks the tile
+//   bins    : 2^bit_depth 32-bit counters per workgroup in LDS (16 KiB at 12 bit), ds_add_u32 per pixel -- or ONE add of the lane count
+//             where every valid lane of the wave holds the same code (flat image areas would serialise 64 adds on one bank)
+//   flush   : once per workgroup (and every kHistFlushTrips trips, before a 32-bit counter could wrap) the non-zero bins go to the
+//             64-bit global bins as per-lane vector atomic adds, 512 contiguous bytes per wave instruction.  Integer adds commute: the
+//             result does not depend on the grid, the tiling or the number of contexts.
+#if AG_WRITE_PART == 0 || AG_WRITE_PART == 40
+#ifndef AG_HIST_BLOCK
+#define AG_HIST_BLOCK 1024
+#endif
+constexpr int kHistWaves = AG_HIST_BLOCK / 64;
+constexpr int kHistPxt = 4;
+constexpr int kHistMaxBlocks = 512;                    // two per CU: 512 x 4096 bins x 8 B = 16 MiB of atomic adds at most per launch
+constexpr uint32_t kHistFlushTrips = 1u << 18;         // 2^18 trips x 1024 lanes x 4 pixels = 2^30 counts per workgroup between flushes
+// A/B hook: 1 = aligned rows arrive like the streaming kernels' -- the wave's span as fully coalesced non-temporal 16-byte loads, transposed
+// to lane-major through a wave-private LDS strip (3 KiB per wave for RGB: build with -DAG_HIST_BLOCK=512) -- instead of lane-strided loads.
+// Measured; 0 = the generic kernel's loads.
+#ifndef AG_HIST_SPAN
+#define AG_HIST_SPAN 0
+#endif
+constexpr size_t kHistMaxTableLds = 40 * 1024;         // 16 KiB of bins + 4 KiB PQ table + this stay inside 64 KiB
+
+AG_DEV void hist_add(uint32_t* bins, uint32_t m, bool valid, int lane)
+{
+    const uint64_t vm = __ballot(valid);
+    if (vm == 0) return;
+    const int first = __builtin_ctzll(vm);
+    const uint32_t m0 = (uint32_t)__builtin_amdgcn_readlane((int)m, first);
+    if (__ballot(valid && m == m0) == vm) {
+        if (lane == first) atomicAdd(&bins[m0], (uint32_t)__builtin_popcountll(vm));
+    } else if (valid) {
+        atomicAdd(&bins[m], 1u);
+    }
+}
+AG_DEV void hist_flush(uint32_t* bins, const HistParams& h)
+{
+    __syncthreads();
+    for (int i = threadIdx.x; i < h.nbins; i += AG_HIST_BLOCK) {
+        const uint32_t c = bins[i];
+        if (c) { atomicAdd(&h.bins[i], (unsigned long long)c); bins[i] = 0; }
+    }
+    __syncthreads();
+}
+
+// TWIN (avifgpu_probe_histogram, timing only -- the counts are meaningless): 1 = atomics-free, the codes are summed in a register
+// instead of counted in LDS; 2 = math-free, no curve: the bin is taken from the sample's bits.  Instantiated for RGB without a profile.
+template <int PLANES, int TRANSFER, bool ALIGNED, int ICC, int TWIN = 0>
+__global__ __launch_bounds__(AG_HIST_BLOCK) void write_hist_px(const WriteParams p, const HistParams h)
+{
+    pq_prologue<TRANSFER>();
+    constexpr int PXT = kHistPxt;
+    constexpr int BPP = PLANES * 4;
+    constexpr int ND = PXT * PLANES;
+    constexpr bool COLOR = PLANES >= 3;
+    __shared__ uint32_t bins[4096];
+    constexpr bool SPAN = AG_HIST_SPAN && ALIGNED;
+    __shared__ __attribute__((aligned(16))) uint32_t strips[SPAN ? kHistWaves : 1][SPAN ? WaveSpan<ND>::STRIP_DW : 1];
+    for (int i = threadIdx.x; i < h.nbins; i += AG_HIST_BLOCK) bins[i] = 0;
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+
+    // the ICC stages' per-workgroup tables, as write_px sets them up: a second copy of that set-up, of its icc = 6 / 8 blocks in front of
+    // stage_a and (launch_hist_icc) of launch_one's choice of ICC -- write_px itself had to keep its instruction stream, so nothing was
+    // moved out of it.  KEEP IN STEP with write_px; tests/test_gpu_light_level.py holds the two equal (hot-variant word 0, every ICC entry)
+    extern __shared__ uint32_t icc6_pairs[];
+    const bool icc6_lds = ICC == 6 && p.icc_s_lds != 0;
+    const int icc6_off[3] = { 0, p.icc_s_n[0], p.icc_s_n[0] + p.icc_s_n[1] };
+    if constexpr (ICC == 6) {
+        if (icc6_lds) {
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                const uint16_t* t16 = p.icc_s_tab16 + ch * AVIFGPU_ICC_SAMPLED_MAX;
+                const int n = p.icc_s_n[ch];
+                for (int i = threadIdx.x; i < n; i += AG_HIST_BLOCK) icc6_pairs[icc6_off[ch] + i] = (uint32_t)t16[i] | ((uint32_t)t16[min(i + 1, n - 1)] << 16);
+            }
+        }
+    }
+    const uint16_t* icc8_words = nullptr;
+    if constexpr (ICC == 8) {
+        icc8_words = p.icc_p8_words;
+        if (p.icc_p8_lds_words) {
+            const uint32_t* g32 = reinterpret_cast<const uint32_t*>(p.icc_p8_words);
+            const int n32 = (p.icc_p8_lds_words + 1) >> 1;
+            for (int i = threadIdx.x; i < n32; i += AG_HIST_BLOCK) icc6_pairs[i] = g32[i];
+            icc8_words = reinterpret_cast<const uint16_t*>(icc6_pairs);
+        }
+    }
+    constexpr bool ICCPOW = (ICC == 2 || ICC == 4);
+    constexpr bool ICCF = IccF32<ICC>::value;
+    __shared__ double icc_pow_L[(ICCPOW && !ICCF) ? kIccPowBins : 1];
+    __shared__ float icc_pow_c[(ICCPOW && !ICCF) ? kIccPowBins : 1];
+    __shared__ __attribute__((aligned(16))) f32x4_t icc_pow_tf[(ICCF && !AG_ICC_FASTPOW) ? kIccPowBins : 1];
+    if constexpr (ICCPOW) {
+        if constexpr (ICCF) icc_pow_table_fill_f(icc_pow_tf, p.icc_pow_tab, threadIdx.x); else icc_pow_table_fill(icc_pow_L, icc_pow_c, threadIdx.x);
+    }
+    const IccPowTable powT = { icc_pow_L, icc_pow_c };
+    const IccPowTableF powTf = { icc_pow_tf };
+    IccRegs iccRegs;
+    IccRegsF iccRegsF;
+    if constexpr (COLOR && (ICC == 1 || ICC == 2 || ICC == 4)) icc_regs_load<ICCF ? 1 : ICC>(p, iccRegs);
+    if constexpr (COLOR && ICCF) icc_regs_load_f<ICC>(p, iccRegsF);
+    __syncthreads();
+
+    const uint32_t gxn = (uint32_t)(p.width + PXT - 1) / PXT;
+    const uint32_t wpr = (gxn + 63u) >> 6;                       // waves per row
+    const uint32_t total_waves = wpr * (uint32_t)p.nrows;        // < 2^31 - grid (host checks)
+    const uint32_t maxbin = (uint32_t)h.nbins - 1u;
+    uint32_t trips = 0;
+    uint32_t twin_acc = 0;
+    // the trip count is the same for every wave of the workgroup (the flushes hold barriers); a wave beyond the tile idles through its last trip
+    for (uint32_t base = blockIdx.x * kHistWaves; base < total_waves; base += gridDim.x * kHistWaves) {
+        const uint32_t wv = base + (uint32_t)wave;
+        const bool wave_on = wv < total_waves;
+        const uint32_t gy = wave_on ? wv / wpr : 0u;
+        const uint32_t wx = wave_on ? wv - gy * wpr : 0u;
+        const uint32_t gx = wx * 64u + (uint32_t)lane;
+        const bool active = wave_on && gx < gxn;
+        const int x0 = (int)(gx * PXT);
+        const int nvalid = active ? min(PXT, p.width - x0) : 0;
+        const uint8_t* rowp = p.src + (long long)gy * p.src_row_bytes;
+        uint32_t s[PXT][PLANES];
+        if constexpr (SPAN) {                                    // the whole wave, active lanes or not: the transfers are wave-wide; zeros beyond the row
+            uint32_t raw[ND];
+            const int span_px = wave_on ? min(64 * PXT, p.width - (int)wx * 64 * PXT) : 0;
+            wave_span_load<ND>(strips[wave], lane, rowp + (long long)wx * (64 * PXT * BPP), span_px * BPP, raw);
+#pragma unroll
+            for (int i = 0; i < PXT; ++i)
+#pragma unroll
+                for (int k = 0; k < PLANES; ++k) s[i][k] = raw[i * PLANES + k];
+        } else if (nvalid == PXT) {
+            uint32_t raw[ND];
+            load_dwords<ND, true, ALIGNED>(rowp + (long long)x0 * BPP, raw);
+#pragma unroll
+            for (int i = 0; i < PXT; ++i)
+#pragma unroll
+                for (int k = 0; k < PLANES; ++k) s[i][k] = raw[i * PLANES + k];
+        } else if (active) {
+#pragma unroll
+            for (int i = 0; i < PXT; ++i) {
+                const uint8_t* pp = rowp + (long long)min(x0 + i, p.width - 1) * BPP;
+#pragma unroll
+                for (int k = 0; k < PLANES; ++k) s[i][k] = ld_u32(pp + 4 * k);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < PXT; ++i)
+#pragma unroll
+                for (int k = 0; k < PLANES; ++k) s[i][k] = 0;
+        }
+        if constexpr (ICC == 6 && COLOR) {                       // sampled document curves in front of stage_a, as in write_px
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                if (p.icc_s_par & (1 << k)) {
+                    if (!p.icc_trc_linear[k]) {
+                        const IccPowTableF noT = { nullptr };
+#pragma unroll
+                        for (int i = 0; i < PXT; ++i) s[i][k] = __float_as_uint(icc_trc_f(noT, p.icc_trc_f[k], __uint_as_float(s[i][k])));
+                    }
+                } else if (icc6_lds) {
+#pragma unroll
+                    for (int i = 0; i < PXT; ++i)
+                        s[i][k] = __float_as_uint(icc_sampled_curve_lds(icc6_pairs + icc6_off[k], (uint32_t)p.icc_s_n[k] - 1u, __uint_as_float(s[i][k])));
+                } else {
+#pragma unroll
+                    for (int i = 0; i < PXT; ++i) s[i][k] = __float_as_uint(icc_sampled_curve(p, k, __uint_as_float(s[i][k])));
+                }
+            }
+        }
+        if constexpr (ICC == 8 && COLOR) {                       // the stage program, as in write_px
+            const avifgpu_icc_stage32* stages = static_cast<const avifgpu_icc_stage32*>(p.icc_p8_stages);
+#pragma unroll
+            for (int i = 0; i < PXT; ++i) {
+                const Icc8Px o = icc8_eval_pixel(stages, p.icc_p8_nstages, icc8_words,
+                                                 Icc8Px{ __uint_as_float(s[i][0]), __uint_as_float(s[i][1]), __uint_as_float(s[i][2]) });
+                s[i][0] = __float_as_uint(o.r); s[i][1] = __float_as_uint(o.g); s[i][2] = __float_as_uint(o.b);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < PXT; ++i) {
+            uint32_t q[4] = { 0, 0, 0, 0 };
+            if constexpr (TWIN == 2) { q[0] = s[i][0] >> 11; q[1] = q[2] = 0; }      // mantissa bits: spread like the codes of noise, equal on a flat frame
+            else stage_a<32, PLANES, TRANSFER, ICC>(p, s[i], q, nullptr, nullptr, nullptr, powT, &iccRegs, powTf, &iccRegsF, nullptr);
+            uint32_t m = q[0];
+            if constexpr (COLOR) m = max(max(q[0], q[1]), q[2]);
+            if constexpr (TWIN == 2) m &= maxbin;
+            if constexpr (TWIN == 1) { twin_acc += i < nvalid ? m : 0u; continue; }
+            hist_add(bins, min(m, maxbin), i < nvalid, lane);    // the codes are clamped to maxValue already; the min keeps the LDS index in bounds whatever the parameters
+        }
+        if (++trips == kHistFlushTrips) { hist_flush(bins, h); trips = 0; }
+    }
+    if constexpr (TWIN == 1) atomicAdd(&bins[threadIdx.x & maxbin], twin_acc);          // keeps the arithmetic alive: one add per lane
+    hist_flush(bins, h);
+}
+
+template <int PLANES, int TRANSFER, int ICC>
+static hipError_t launch_hist_k(const WriteParams& p, const HistParams& h, int blocks, size_t lds, bool aligned, hipStream_t st)
+{
+    if (aligned) hipLaunchKernelGGL((write_hist_px<PLANES, TRANSFER, true, ICC>), dim3(blocks), dim3(AG_HIST_BLOCK), lds, st, p, h);
+    else hipLaunchKernelGGL((write_hist_px<PLANES, TRANSFER, false, ICC>), dim3(blocks), dim3(AG_HIST_BLOCK), lds, st, p, h);
+    return hipGetLastError();
+}
+
+// the ICC stage of the launch, chosen as launch_one chooses it for write_px
+template <int PLANES, int TRANSFER>
+static hipError_t launch_hist_icc(const WriteParams& p0, const HistParams& h, int blocks, bool aligned, hipStream_t st)
+{
+    if constexpr (PLANES >= 3) {
+        WriteParams p = p0;
+        if (p.icc_p8_stages != nullptr) {
+            size_t lds = p.icc_p8_lds_words ? (size_t)((p.icc_p8_lds_words + 1) >> 1) * 4 : 0;
+            if (lds > kHistMaxTableLds) { p.icc_p8_lds_words = 0; lds = 0; }            // the same words, read from device memory
+            return launch_hist_k<PLANES, TRANSFER, 8>(p, h, blocks, lds, aligned, st);
+        }
+        if (p.icc_s_tab != nullptr) {
+            size_t lds = p.icc_s_lds ? (size_t)(p.icc_s_n[0] + p.icc_s_n[1] + p.icc_s_n[2]) * 4 : 0;
+            if (lds > kHistMaxTableLds) { p.icc_s_lds = 0; lds = 0; }                   // curve[] in memory holds the same values (tests/test_gpu_icc.py)
+            return launch_hist_k<PLANES, TRANSFER, 6>(p, h, blocks, lds, aligned, st);
+        }
+        if (p.icc_trc_type[0] != 0) {
+            bool linear = true;
+            for (int c = 0; c < 3; ++c) linear = linear && p.icc_trc_linear[c] != 0;
+            if (p.icc_out == 4) {
+                if constexpr (TRANSFER == 3) return launch_hist_k<PLANES, TRANSFER, 4>(p, h, blocks, 0, aligned, st);
+                else return hipErrorInvalidValue;                                       // rejected earlier by fill_write_params
+            }
+            if (linear) return launch_hist_k<PLANES, TRANSFER, 1>(p, h, blocks, 0, aligned, st);
+            return launch_hist_k<PLANES, TRANSFER, 2>(p, h, blocks, 0, aligned, st);
+        }
+    }
+    return launch_hist_k<PLANES, TRANSFER, 0>(p0, h, blocks, 0, aligned, st);
+}
+
+template <int TRANSFER>
+static hipError_t launch_hist_twin(const WriteParams& p, const HistParams& h, int blocks, int twin, hipStream_t st)
+{
+    if (twin == 1) hipLaunchKernelGGL((write_hist_px<3, TRANSFER, true, 0, 1>), dim3(blocks), dim3(AG_HIST_BLOCK), 0, st, p, h);
+    else hipLaunchKernelGGL((write_hist_px<3, TRANSFER, true, 0, 2>), dim3(blocks), dim3(AG_HIST_BLOCK), 0, st, p, h);
+    return hipGetLastError();
+}
+
+template <int PLANES>
+static hipError_t launch_hist_tr(const WriteParams& p, const HistParams& h, int blocks, bool aligned, hipStream_t st)
+{
+    switch (p.transfer) {
+    case AVIFGPU_TRANSFER_PQ:       if (pq_hi_launch(p)) return launch_hist_icc<PLANES, kTransferPqHi>(p, h, blocks, aligned, st);
+                                    return launch_hist_icc<PLANES, 0>(p, h, blocks, aligned, st);
+    case AVIFGPU_TRANSFER_HLG:      return launch_hist_icc<PLANES, 1>(p, h, blocks, aligned, st);
+    case AVIFGPU_TRANSFER_SMPTE428: return launch_hist_icc<PLANES, 2>(p, h, blocks, aligned, st);
+    default:                        return launch_hist_icc<PLANES, 3>(p, h, blocks, aligned, st);
+    }
+}
+
+// Entry used by avifgpu_api.hip / pipeline.hip behind launch_write() of the same tile: p as that launch got it (the plane pointers are
+// not looked at), bins = 1 << bit_depth 64-bit counters on the device of `st`.  A contiguous tile is walked as one long row.
+hipError_t launch_write_hist(const WriteParams& p0, int planes, unsigned long long* bins, hipStream_t st, int twin)
+{
+    if (planes < 1 || planes > 4 || bins == nullptr || (p0.maxv != 1023 && p0.maxv != 4095)) return hipErrorInvalidValue;
+    WriteParams p = p0;
+    const long long px = (long long)p.width * p.nrows;
+    if (px == 0) return hipSuccess;
+    if (p.nrows > 1 && px < (1LL << 30) && p.src_row_bytes == (long long)p.width * planes * 4) {
+        p.width = (int32_t)px; p.nrows = 1; p.src_row_bytes = px * planes * 4;
+    }
+    const long long waves = (((long long)p.width + kHistPxt - 1) / kHistPxt + 63) / 64 * p.nrows;
+    if (waves >= 0x7fffffffLL - (long long)kHistMaxBlocks * kHistWaves) return hipErrorInvalidValue;       // 32-bit wave index in the kernel
+    long long blocks = (waves + kHistWaves - 1) / kHistWaves;
+    if (blocks > kHistMaxBlocks) blocks = kHistMaxBlocks;
+    const bool aligned = ((reinterpret_cast<uintptr_t>(p.src) | (uintptr_t)p.src_row_bytes) & 15) == 0;
+    const HistParams h = { bins, p.maxv + 1 };
+    if (twin) {                                            // the timing twins: aligned RGB rows, PQ, no profile
+        if ((twin != 1 && twin != 2) || planes != 3 || !aligned || p.transfer != AVIFGPU_TRANSFER_PQ || p.icc_trc_type[0] != 0) return hipErrorInvalidValue;
+        return pq_hi_launch(p) ? launch_hist_twin<kTransferPqHi>(p, h, (int)blocks, twin, st) : launch_hist_twin<AVIFGPU_TRANSFER_PQ>(p, h, (int)blocks, twin, st);
+    }
+    switch (planes) {
+    case 1:  return launch_hist_tr<1>(p, h, (int)blocks, aligned, st);
+    case 2:  return launch_hist_tr<2>(p, h, (int)blocks, aligned, st);
+    case 3:  return launch_hist_tr<3>(p, h, (int)blocks, aligned, st);
+    default: return launch_hist_tr<4>(p, h, (int)blocks, aligned, st);
+    }
+}
+#endif   // AG_WRITE_PART == 0 || 40
 
 #if AG_WRITE_PART == 0 || AG_WRITE_PART == 1
 static hipError_t launch_write_impl(const WriteParams& p, int depth, int planes, bool dst16, int output, int xs, int ys,

@@ -94,6 +94,7 @@ HOST_ABI = [
     ("avifgpu_host_chroma_subsampling", c_int32, [c_int32, c_int32]),
     ("avifgpu_host_interleaved_chroma", c_int32, [c_int32, c_int32]),
     ("avifgpu_host_normalize_save_options", c_int16, [POINTER(FormatRecord), POINTER(SaveUIOptions)]),
+    ("avifgpu_host_save_wants_light_level", c_int32, [POINTER(FormatRecord), POINTER(SaveUIOptions)]),
     ("avifgpu_host_alpha_state", c_int32, [POINTER(FormatRecord), POINTER(SaveUIOptions)]),
     ("avifgpu_host_required_conversion", c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
     ("avifgpu_host_required_conversion_for_record", c_int32, [POINTER(FormatRecord), POINTER(SaveUIOptions)]),

@@ -315,6 +315,42 @@ int32_t avifgpu_write_rows(const avifgpu_write_desc* desc,
                            void* const dst[4], const int64_t dst_stride[4],
                            int32_t mem_kind, void* stream);
 
+/* ---- content light level of an HDR save (clli: MaxCLL / MaxFALL, CTA-861.3 Annex P) ----------------------------------------------
+ * An extension: the reference does not compute it.  The statistic is a histogram of the brightest stage-A code of each pixel --
+ * m = max(R, G, B) (gray: Y) of the integer codes the 32-bit write loops hand to libheif (after the ICC row transform, the alpha
+ * clamp and the optional premultiply, before any YCbCr step; alpha codes are not counted), count[m] += 1 -- taken by a kernel of
+ * its own behind the conversion of the same rows.  Integer counts add in any order: the result is the same for every tiling, every
+ * number of bound devices and every launch shape.
+ *
+ * Arm (bins != NULL) or disarm (NULL) the calling thread's code histogram.  While armed, every avifgpu_write_rows* call of this
+ * thread on a depth-32 descriptor adds its rows' pixels to bins[0 .. (1 << bit_depth) - 1] (bit_depth 10 or 12, anything else is
+ * formatBadParameters here); calls at depth 8 / 16 and every read are unaffected and do not touch it.  The FormatRecord shim's
+ * saves (avifgpu_host.h) run on the caller's thread and honour it with mem_kind HOST, all tiles of a save summed.  The library
+ * never zeroes the bins.  mem_kind says where bins live and must equal the mem_kind of the calls: HOST -- the counts are complete
+ * when each call returns (a call that fails adds nothing); DEVICE -- the adds are enqueued on the call's stream behind its kernel.
+ * A call whose desc->bit_depth differs from the armed one, or whose mem_kind differs, fails with formatBadParameters before
+ * anything is launched.  Host-only bookkeeping: needs no device. */
+int32_t avifgpu_histogram_attach(uint64_t* bins, int32_t bit_depth, int32_t mem_kind);
+
+typedef struct avifgpu_content_light_level {
+    uint16_t max_cll, max_fall;       /* the clli fields: min(65535, floor(nits + 0.5)) */
+    int32_t  max_code;                /* c_p: the smallest code with sum_{k <= c_p} count[k] >= ceil(percentile * pixels) */
+    uint64_t pixels;                  /* n = sum of the bins */
+    double   max_cll_nits, max_fall_nits;
+} avifgpu_content_light_level;
+
+/* Host only, float64.  For PQ at bit depth b code c stands for L(c) = 10000 * EOTF_PQ(c / (2^b - 1)) cd/m2 (SMPTE ST 2084 with its
+ * exact rational constants; the codes in the file are absolute, peak_nits plays no part).  max_cll_nits = L(c_p); max_fall_nits =
+ * (sum_c count[c] L(c)) / n, summed in ascending code order.  percentile in (0, 1]; 1 gives the highest non-empty bin.  Any other
+ * transfer, an empty histogram, a bit depth other than 10 or 12 or a percentile outside (0, 1] is formatBadParameters. */
+int32_t avifgpu_light_level_from_histogram(const uint64_t* bins, int32_t bit_depth, int32_t transfer, double percentile,
+                                           avifgpu_content_light_level* out);
+
+/* Measuring aid (tools/bench_light_level.py): launch the histogram kernel of `desc` (depth 32) ALONE on the whole frame at device pointer
+ * `src`, into device bins, on `stream`.  twin 0 = the kernel itself (the same counts an armed avifgpu_write_rows adds); 1 / 2 = its
+ * atomics-free / math-free twin for attribution (RGB, PQ, no profile, 16-byte aligned rows; the counts they leave are meaningless). */
+int32_t avifgpu_probe_histogram(const avifgpu_write_desc* desc, int32_t twin, const void* src, int64_t src_row_bytes, uint64_t* bins, void* stream);
+
 /*
  * Inverse direction.  src[i] / src_stride[i] are what heif_image_get_plane_readonly returns
  * (ReadHeifImage.cpp:104-111) advanced to row `row0` (chroma: row0 >> yShift); plane order is

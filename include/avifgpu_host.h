@@ -210,6 +210,12 @@ int32_t avifgpu_host_interleaved_chroma(int32_t bit_depth, int32_t has_alpha);
  * first rule).  imageBitDepth is the NUMBER (8|10|12) here, as everywhere in avifgpu_SaveUIOptions. */
 avifgpu_OSErr avifgpu_host_normalize_save_options(const avifgpu_FormatRecord* formatRecord, avifgpu_SaveUIOptions* saveOptions);
 
+/* Whether a save should carry a content light level (clli; an extension, include/avifgpu.h "content light level"): 1 exactly for a
+ * depth-32 save whose transfer, after avifgpu_host_normalize_save_options, is PQ -- the adapter then arms avifgpu_histogram_attach
+ * around its avifgpu_host_create_heif_image* call; 0 otherwise; AVIFGPU_formatBadParameters for a null argument.  The options
+ * are not modified. */
+int32_t avifgpu_host_save_wants_light_level(const avifgpu_FormatRecord* formatRecord, const avifgpu_SaveUIOptions* saveOptions);
+
 /* GetAlphaState (Write.cpp:189-208): AVIFGPU_ALPHA_NONE without an alpha plane (HasAlphaChannel, Utilities.cpp:418-432),
  * PREMULTIPLIED when premultipliedAlpha && !lossless, else STRAIGHT. */
 int32_t avifgpu_host_alpha_state(const avifgpu_FormatRecord* formatRecord, const avifgpu_SaveUIOptions* saveOptions);
