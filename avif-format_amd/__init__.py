@@ -228,6 +228,10 @@ ABI = [
     ("avifgpu_histogram_attach", c_int32, [c_void_p, c_int32, c_int32]),
     ("avifgpu_light_level_from_histogram", c_int32, [c_void_p, c_int32, c_int32, ctypes.c_double, POINTER(ContentLightLevel)]),
     ("avifgpu_probe_histogram", c_int32, [POINTER(WriteDesc), c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
+    ("avifgpu_thumbnail_attach", c_int32, [c_void_p, c_int32, c_int32, c_int32]),
+    ("avifgpu_thumbnail_fit", c_int32, [POINTER(WriteDesc), c_int32, POINTER(c_int32), POINTER(c_int32)]),
+    ("avifgpu_thumbnail_from_sums", c_int32, [POINTER(WriteDesc), c_int32, c_int32, c_void_p, POINTER(_PLANES4), POINTER(_STRIDES4)]),
+    ("avifgpu_probe_thumbnail", c_int32, [POINTER(WriteDesc), c_int32, c_int32, c_int32, POINTER(_PLANES4), POINTER(_STRIDES4), c_void_p, c_void_p]),
 ]
 
 
@@ -239,7 +243,8 @@ ABI4_NEW = frozenset(("avifgpu_probe_pattern_read", "avifgpu_probe_pattern_rgb32
                       "avifgpu_icc_clut16_from_transforms",
                       "avifgpu_icc_clut8_from_transforms", "avifgpu_write_rows_icc8_table", "avifgpu_probe_set_shape",        # (ABI 5, round 6)
                       "avifgpu_histogram_attach", "avifgpu_light_level_from_histogram", "avifgpu_probe_histogram",
-                      "avifgpu_host_save_wants_light_level"))   # (the code histogram)
+                      "avifgpu_host_save_wants_light_level",    # (the code histogram)
+                      "avifgpu_thumbnail_attach", "avifgpu_thumbnail_fit", "avifgpu_thumbnail_from_sums", "avifgpu_probe_thumbnail"))   # (the thumbnail)
 
 
 def bind(lib: ctypes.CDLL, table=ABI) -> ctypes.CDLL:
@@ -475,6 +480,79 @@ def light_level_from_histogram(bins, bit_depth: int, transfer=TRANSFER_PQ, perce
     if code != 0:
         raise AvifGpuError(code, lib.avifgpu_last_error().decode())
     return out
+
+
+class thumbnail_sums:
+    """Arm the calling thread's thumbnail sums for the `with` block, disarm them on the way out (avifgpu_thumbnail_attach).
+
+    `sums` holds tw * th * planes 64-bit counters, [(ty * tw + tx) * planes + c], and is never zeroed by the library: a numpy uint64
+    array (mem = MEM_HOST), a contiguous torch int64 / uint64 tensor on the device the calls run on (mem = MEM_DEVICE), or a raw address."""
+
+    def __init__(self, sums, tw: int, th: int, mem=MEM_HOST):
+        self.sums, self.tw, self.th, self.mem = sums, int(tw), int(th), mem
+
+    def _address(self):
+        b = self.sums
+        if hasattr(b, "data_ptr"):
+            n, ptr = b.numel(), b.data_ptr()
+            if b.element_size() != 8 or not b.is_contiguous():
+                raise ValueError("thumbnail_sums: sums must be contiguous 64-bit counters")
+        elif hasattr(b, "ctypes"):
+            n, ptr = b.size, b.ctypes.data
+            if b.dtype.itemsize != 8 or not b.flags["C_CONTIGUOUS"]:
+                raise ValueError("thumbnail_sums: sums must be contiguous 64-bit counters")
+        else:
+            return int(b)
+        if n < self.tw * self.th:
+            raise ValueError("thumbnail_sums: %d counters for a %dx%d thumbnail" % (n, self.tw, self.th))
+        return ptr
+
+    def __enter__(self):
+        lib = load()
+        code = lib.avifgpu_thumbnail_attach(self._address(), self.tw, self.th, self.mem)
+        if code != 0:
+            raise AvifGpuError(code, lib.avifgpu_last_error().decode())
+        return self
+
+    def __exit__(self, *exc):
+        load().avifgpu_thumbnail_attach(None, 0, 0, MEM_HOST)
+        return False
+
+
+def thumbnail_fit(desc: WriteDesc, bbox: int):
+    """(tw, th) of an aspect-preserving fit of the save into a bbox x bbox square: avifgpu_thumbnail_fit."""
+    lib = load()
+    tw, th = c_int32(0), c_int32(0)
+    code = lib.avifgpu_thumbnail_fit(ctypes.byref(desc), bbox, ctypes.byref(tw), ctypes.byref(th))
+    if code != 0:
+        raise AvifGpuError(code, lib.avifgpu_last_error().decode())
+    return tw.value, th.value
+
+
+def thumbnail_from_sums(desc: WriteDesc, tw: int, th: int, sums, stride_pad: int = 0):
+    """The thumbnail planes of host sums (numpy uint64, tw * th * planes): avifgpu_thumbnail_from_sums.  Returns {plane: array} in the
+    form of the main output -- plane 0 (th, tw * planes) for a colour REFERENCE save, planes 0 (+ 3) for gray, 0, 1, 2 (+ 3) at
+    tw x th for YCBCR output; uint8 at bit depth 8, uint16 otherwise.  stride_pad: extra samples per row (they keep their 0xA5 fill)."""
+    import numpy as np
+    lib = load()
+    if sums.dtype.itemsize != 8 or not sums.flags["C_CONTIGUOUS"] or sums.size < tw * th * desc.planes:
+        raise ValueError("thumbnail_from_sums: sums must be tw * th * planes contiguous 64-bit counters")
+    dt = np.uint16 if desc.bit_depth > 8 else np.uint8
+    color = desc.planes >= 3
+    alpha = desc.planes in (2, 4)
+    if desc.output == OUT_REFERENCE:
+        shapes = {0: tw * desc.planes} if color else ({0: tw, 3: tw} if alpha else {0: tw})
+    else:
+        shapes = {0: tw, 1: tw, 2: tw}
+        if alpha:
+            shapes[3] = tw
+    bufs = {pl: np.full((max(th, 1), w + stride_pad), 0xA5A5 if dt == np.uint16 else 0xA5, dtype=dt) for pl, w in shapes.items()}
+    ptrs = _PLANES4(*[bufs[i].ctypes.data if i in bufs else None for i in range(4)])
+    strides = _STRIDES4(*[bufs[i].strides[0] if i in bufs else 0 for i in range(4)])
+    code = lib.avifgpu_thumbnail_from_sums(ctypes.byref(desc), tw, th, sums.ctypes.data, ctypes.byref(ptrs), ctypes.byref(strides))
+    if code != 0:
+        raise AvifGpuError(code, lib.avifgpu_last_error().decode())
+    return bufs
 
 
 def yuv_coefficients(has_nclx: int, matrix: int, primaries: int):

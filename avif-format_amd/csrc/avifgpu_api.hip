@@ -800,6 +800,8 @@ int write_rows_any(const avifgpu_write_desc* d, const IccArgs& icc, int32_t row0
     if (context_count() == 0) return fail(AVIFGPU_formatBadParameters, "%s", kNoDevice);
     uint64_t* hist = nullptr;
     if ((err = histogram_for_call(d, mem_kind, &hist))) return err;            // before anything is launched
+    ThumbArm thumb;
+    if ((err = thumbnail_for_call(d, g, mem_kind, &thumb))) return err;        // likewise
     if (nrows == 0) return 0;
     if (icc.c16 || icc.s32 || icc.c8t) icc_epoch_for_call(row0, nrows);       // the device copies of these tables are re-verified once per device and epoch
 
@@ -815,6 +817,10 @@ int write_rows_any(const avifgpu_write_desc* d, const IccArgs& icc, int32_t row0
         if (hist) {                                     // the statistics kernel behind it on the caller's stream, straight into the caller's device bins
             const hipError_t eh = launch_write_hist(p, d->planes, reinterpret_cast<unsigned long long*>(hist), st);
             if (eh != hipSuccess) return hip_fail(eh, "histogram kernel launch", AVIFGPU_writErr);
+        }
+        if (thumb.sums) {                               // the planes just written, summed behind it on the caller's stream into the caller's device sums
+            const hipError_t et = launch_thumbnail(d, g, row0, nrows, p.dst, p.dst_stride, thumb.tw, thumb.th, reinterpret_cast<unsigned long long*>(thumb.sums), st);
+            if (et != hipSuccess) return hip_fail(et, "thumbnail kernel launch", AVIFGPU_writErr);
         }
         return 0;
     }

@@ -36,11 +36,11 @@ avifgpu_OSErr advance_state()
 uint8_t never_abort() { return 0; }
 
 struct Args {
-    std::string cmd, in, out, icc;
+    std::string cmd, in, out, icc, thumb_out;
     int width = 0, height = 0, depth = 8, planes = 3, bits = 8, transfer = AVIFGPU_TRANSFER_CLIP, peak = 1000;
     int alpha = AVIFGPU_ALPHA_NONE, output = AVIFGPU_OUT_REFERENCE, chroma = AVIFGPU_CHROMA_444;
     int matrix = AVIFGPU_MATRIX_BT601, primaries = AVIFGPU_PRIMARIES_BT709, tc = 2, limited = 0, colorspace = AVIFGPU_COLORSPACE_YCBCR;
-    int lossless = 0, maxdata = 0, device = 0, hlg_ootf = 0, nclx = 0, keep_profile = 0, light_level = 0;
+    int lossless = 0, maxdata = 0, device = 0, hlg_ootf = 0, nclx = 0, keep_profile = 0, light_level = 0, thumb_bbox = 0;
     float gamma = 1.2f;
     double percentile = 1.0;
 };
@@ -52,7 +52,7 @@ struct Args {
         "usage: avifgpu_cli write --width W --height H --depth 8|16|32 --planes 1..4 --bits 8|10|12 [--transfer clip|pq|smpte428]\n"
         "                         [--peak NITS] [--alpha none|straight|premultiplied] [--ycbcr 444|422|420] [--matrix N] [--primaries N]\n"
         "                         [--lossless] [--icc PROFILE [--keep-profile]] [--maxdata BYTES] [--device N]\n"
-        "                         [--light-level [--percentile P]] IN.raw OUT.planes\n"
+        "                         [--light-level [--percentile P]] [--thumbnail BBOX THUMB.planes] IN.raw OUT.planes\n"
         "       avifgpu_cli read  --width W --height H --depth 8|16|32 --bits 8|10|12 --colorspace ycbcr|rgb|mono [--chroma 444|422|420]\n"
         "                         [--alpha none|straight|premultiplied] [--matrix N --primaries N --tc N [--limited]] [--peak NITS]\n"
         "                         [--hlg-ootf --gamma G] [--maxdata BYTES] [--device N] IN.planes OUT.raw\n");
@@ -93,6 +93,7 @@ Args parse(int argc, char** argv)
         else if (o == "--keep-profile") a.keep_profile = 1;
         else if (o == "--light-level") a.light_level = 1;
         else if (o == "--percentile") a.percentile = atof(val());
+        else if (o == "--thumbnail") { a.thumb_bbox = atoi(val()); a.thumb_out = val(); if (a.thumb_bbox < 1) usage("--thumbnail needs a bounding box >= 1"); }
         else if (o == "--icc") a.icc = val();
         else if (o == "--transfer") a.transfer = pick(val(), {{"clip", AVIFGPU_TRANSFER_CLIP}, {"pq", AVIFGPU_TRANSFER_PQ}, {"smpte428", AVIFGPU_TRANSFER_SMPTE428}}, "--transfer");
         else if (o == "--alpha") a.alpha = pick(val(), {{"none", AVIFGPU_ALPHA_NONE}, {"straight", AVIFGPU_ALPHA_STRAIGHT}, {"premultiplied", AVIFGPU_ALPHA_PREMULTIPLIED}}, "--alpha");
@@ -187,12 +188,52 @@ int do_write(const Args& a)
         const int hrc = avifgpu_histogram_attach(bins.data(), a.bits, AVIFGPU_MEM_HOST);
         if (hrc) return fail("avifgpu_histogram_attach", hrc);
     }
+    // --thumbnail: the box-average thumbnail of the save, its sums armed around the shim's call on this thread (all tiles summed)
+    std::vector<uint64_t> tsums;
+    avifgpu_write_desc td{};
+    int32_t tw = 0, th = 0;
+    if (a.thumb_bbox) {
+        avifgpu_SaveUIOptions n = o;                                // the options the save will run with (Write.cpp:231-258)
+        if (avifgpu_host_normalize_save_options(&g_host.fr, &n) != AVIFGPU_noErr) return fail("avifgpu_host_normalize_save_options", AVIFGPU_formatBadParameters);
+        td.width = a.width; td.height = a.height; td.depth = a.depth; td.planes = a.planes;
+        td.bit_depth = n.imageBitDepth; td.transfer = n.hdrTransferFunction; td.peak_nits = a.peak; td.alpha_state = a.alpha;
+        td.output = a.planes <= 2 ? AVIFGPU_OUT_REFERENCE : a.output;
+        td.chroma = a.lossless ? AVIFGPU_CHROMA_444 : a.chroma;
+        td.matrix_coefficients = a.lossless ? AVIFGPU_MATRIX_RGB_GBR : a.matrix; td.color_primaries = a.primaries;
+        td.full_range = 1; td.chroma_downsampling = AVIFGPU_DOWNSAMPLE_AVERAGE; td.chroma_zero_point = AVIFGPU_CHROMA_ZERO_LIBHEIF;
+        int trc = avifgpu_thumbnail_fit(&td, a.thumb_bbox, &tw, &th);
+        if (trc) return fail("avifgpu_thumbnail_fit", trc);
+        tsums.assign((size_t)tw * th * a.planes, 0);
+        if ((trc = avifgpu_thumbnail_attach(tsums.data(), tw, th, AVIFGPU_MEM_HOST))) return fail("avifgpu_thumbnail_attach", trc);
+    }
     avifgpu_image img{};
     const int rc = avifgpu_host_create_heif_image(&g_host.fr, a.alpha, &o, a.output, a.lossless ? AVIFGPU_MATRIX_RGB_GBR : a.matrix,
                                                   a.primaries, &img);
     fclose(g_host.file);
     if (a.light_level) (void)avifgpu_histogram_attach(nullptr, 0, AVIFGPU_MEM_HOST);
+    if (a.thumb_bbox) (void)avifgpu_thumbnail_attach(nullptr, 0, 0, AVIFGPU_MEM_HOST);
     if (rc) return fail("avifgpu_host_create_heif_image", rc);
+    if (a.thumb_bbox) {
+        // the thumbnail planes in the raw form of the main planes: tight rows, plane after plane
+        const int ssz = td.bit_depth > 8 ? 2 : 1;
+        const bool interleaved = td.output == AVIFGPU_OUT_REFERENCE && a.planes >= 3;
+        std::vector<uint8_t> tp[4];
+        void* tdst[4] = {}; int64_t tstride[4] = {};
+        for (int pl = 0; pl < 4; ++pl) {
+            const bool used = interleaved ? pl == 0 : td.output == AVIFGPU_OUT_REFERENCE ? (pl == 0 || (pl == 3 && a.planes == 2)) : (pl < 3 || a.planes == 4);
+            if (!used) continue;
+            tstride[pl] = (int64_t)tw * (interleaved ? a.planes : 1) * ssz;
+            tp[pl].assign((size_t)tstride[pl] * th, 0);
+            tdst[pl] = tp[pl].data();
+        }
+        const int trc = avifgpu_thumbnail_from_sums(&td, tw, th, tsums.data(), tdst, tstride);
+        if (trc) { avifgpu_image_free(&img); return fail("avifgpu_thumbnail_from_sums", trc); }
+        FILE* tf = fopen(a.thumb_out.c_str(), "wb");
+        if (!tf) { perror(a.thumb_out.c_str()); avifgpu_image_free(&img); return 1; }
+        for (int pl = 0; pl < 4; ++pl) if (tdst[pl] && fwrite(tp[pl].data(), 1, tp[pl].size(), tf) != tp[pl].size()) { perror(a.thumb_out.c_str()); fclose(tf); avifgpu_image_free(&img); return 1; }
+        fclose(tf);
+        printf("thumbnail %dx%d\n", (int)tw, (int)th);
+    }
     if (a.light_level) {
         avifgpu_content_light_level ll{};
         const int lrc = avifgpu_light_level_from_histogram(bins.data(), a.bits, o.hdrTransferFunction, a.percentile, &ll);

@@ -117,6 +117,26 @@ struct HistParams {
     int32_t nbins;               // 1 << bit_depth: 1024 | 4096
 };
 
+// The box-average thumbnail of a save (thumb_box_sums, thumbnail_kernels.hip): integer sums of the output codes a tile's conversion kernel
+// just wrote, per thumbnail cell and channel, added to 64-bit counters in device memory with vector atomics
+struct ThumbPlane {
+    const uint8_t* base;         // the plane at the tile's first row (chroma: row0 >> ys), as the conversion kernel was given it
+    int64_t stride;              // bytes
+    int32_t pw, ph;              // the WHOLE plane's size in pixels: the cell rule is floor(x tw / pw), floor(y th / ph)
+    int32_t prow0, prows;        // the tile's first plane row and its plane rows
+    int32_t c0;                  // channel of the plane's first interleaved channel in the sums (R,G,B[,A] | Y[,A] | Y,Cb,Cr[,A])
+    int32_t aligned;             // base and stride are multiples of 16: rows are read as 16-byte loads
+};
+struct ThumbParams {
+    ThumbPlane pl[4];            // grid.z picks one
+    unsigned long long* sums;    // [(ty * tw + tx) * C + c]
+    int32_t nslots;              // entries of pl[] in use
+    int32_t tw, th, C;
+    int32_t band_rows;           // consecutive plane rows per workgroup (launch_thumbnail)
+    int32_t lds_entries;         // 64-bit LDS counters per workgroup: the (cell, channel) pairs a column block can touch
+    int32_t twin;                // 1: avifgpu_probe_thumbnail's atomics-free twin (loads and register adds only; sums are not produced)
+};
+
 struct ReadParams {
     const uint8_t* src[4];       // Y,Cb,Cr,A / R,G,B,A / Y,-,-,A at row row0 (chroma: row0 >> ys)
     int64_t        src_stride[4];

@@ -62,6 +62,7 @@ struct Job {
     void* rows_out = nullptr;        int64_t rows_out_stride = 0;
     IccArgs icc;
     bool hist = false;                                     // write, depth 32: the calling thread had a code histogram armed (enqueue side decides, the worker counts)
+    int thumb_tw = 0, thumb_th = 0;                        // write: the calling thread had a thumbnail of this size armed (0: none)
     // filled by start(): what finish() still has to copy out of the pinned bounce buffer
     struct Bounce { uint8_t* dst; int64_t dst_stride; size_t off, pitch, bytes; int rows; } bounce[4];
     int nbounce = 0;
@@ -104,6 +105,12 @@ struct Ctx {
     // device, allocated and zeroed by the worker on first use, freed when it exits; wait_all() adds them to the caller's bins and zeroes them
     unsigned long long* d_hist = nullptr;
     std::atomic<bool> hist_dirty{false};
+    // thumbnail sums of the tiles this context converted for an armed caller (avifgpu_thumbnail_attach): [(ty * tw + tx) * C + c] on the
+    // device, grown and zeroed by the worker; wait_all() adds thumbnail rows [thumb_lo, thumb_hi) -- the only ones touched since it last
+    // ran -- to the caller's sums and zeroes them.  Written by the worker only, read by wait_all() when the context is idle (Ctx::mu orders them).
+    unsigned long long* d_thumb = nullptr;
+    size_t d_thumb_cap = 0;                                // counters
+    int thumb_tw = 0, thumb_th = 0, thumb_c = 0, thumb_lo = 0, thumb_hi = 0;
 };
 constexpr int kHistBins = 4096;
 
@@ -525,6 +532,27 @@ int start_write(Ctx& c, Job& j)
         e = launch_write_hist(p, d->planes, c.d_hist, st);
         if (e != hipSuccess) { (void)hipStreamSynchronize(st); return hip_fail(e, "histogram kernel launch", AVIFGPU_writErr); }
     }
+    if (j.thumb_tw > 0) {
+        // the thumbnail sums of the planes that lie in d_out, likewise behind their copies back (which only read d_out, as this does)
+        const size_t need = (size_t)j.thumb_tw * (size_t)j.thumb_th * (size_t)d->planes;
+        if (need > c.d_thumb_cap) {                        // first armed tile, or a larger thumbnail than before: nothing of this call is in flight yet
+            if (c.d_thumb) { (void)hipFree(c.d_thumb); c.d_thumb = nullptr; c.d_thumb_cap = 0; }
+            void* tb = nullptr;
+            e = hipMalloc(&tb, need * sizeof(unsigned long long));
+            if (e == hipSuccess) e = hipMemsetAsync(tb, 0, need * sizeof(unsigned long long), st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);          // the other slots' streams add into it too
+            if (e != hipSuccess) { if (tb) (void)hipFree(tb); (void)hipStreamSynchronize(st); return hip_fail(e, "hipMalloc(thumbnail sums)", AVIFGPU_memFullErr); }
+            c.d_thumb = static_cast<unsigned long long*>(tb); c.d_thumb_cap = need;
+            c.thumb_lo = c.thumb_hi = 0;
+        }
+        int lo, hi;
+        thumbnail_rows_of_tile(d, g, j.row0, j.nrows, j.thumb_th, lo, hi);
+        if (c.thumb_hi <= c.thumb_lo) { c.thumb_lo = lo; c.thumb_hi = hi; }
+        else { c.thumb_lo = std::min(c.thumb_lo, lo); c.thumb_hi = std::max(c.thumb_hi, hi); }
+        c.thumb_tw = j.thumb_tw; c.thumb_th = j.thumb_th; c.thumb_c = d->planes;
+        e = launch_thumbnail(d, g, j.row0, j.nrows, p.dst, p.dst_stride, j.thumb_tw, j.thumb_th, c.d_thumb, st);
+        if (e != hipSuccess) { (void)hipStreamSynchronize(st); return hip_fail(e, "thumbnail kernel launch", AVIFGPU_writErr); }
+    }
     if ((e = hipEventRecord(sl.done, st)) != hipSuccess) { (void)hipStreamSynchronize(st); return hip_fail(e, "event record", AVIFGPU_writErr); }
     return 0;
 }
@@ -728,6 +756,7 @@ void worker_main(Ctx* cp)
         sl = Slot();
     }
     if (c.d_hist) { (void)hipFree(c.d_hist); c.d_hist = nullptr; }
+    if (c.d_thumb) { (void)hipFree(c.d_thumb); c.d_thumb = nullptr; c.d_thumb_cap = 0; c.thumb_lo = c.thumb_hi = 0; }
 }
 
 Ctx* ctx_at(int i)
@@ -975,6 +1004,9 @@ int write_tile_enqueue(int ctx, int slot, const avifgpu_write_desc* d, int row0,
     uint64_t* hist = nullptr;                              // the arming is the calling thread's; a mismatch fails here, before anything is queued
     if ((err = histogram_for_call(d, AVIFGPU_MEM_HOST, &hist))) return err;
     j.hist = hist != nullptr;
+    ThumbArm thumb;                                        // likewise
+    if ((err = thumbnail_for_call(d, g, AVIFGPU_MEM_HOST, &thumb))) return err;
+    if (thumb.sums) { j.thumb_tw = thumb.tw; j.thumb_th = thumb.th; }
     return enqueue(ctx, j);
 }
 
@@ -1030,6 +1062,31 @@ int collect_histograms(bool discard)
     if (cur >= 0) (void)hipSetDevice(cur);
     return rc;
 }
+// Likewise for the thumbnail sums: only the thumbnail rows the contexts' tiles touched are read back and zeroed.  They are added to the
+// calling thread's armed HOST sums when those still have the size the tiles were summed for.
+int collect_thumbnails(bool discard)
+{
+    int tw = 0, th = 0;
+    uint64_t* sums = discard ? nullptr : thumbnail_host_sums(&tw, &th);
+    int cur = -1, rc = 0;
+    std::vector<unsigned long long> tmp;
+    for (int i = 0; i < context_count(); ++i) {
+        Ctx* c = ctx_at(i);
+        if (!c->d_thumb || c->thumb_hi <= c->thumb_lo) continue;
+        if (cur == -1 && hipGetDevice(&cur) != hipSuccess) { (void)hipGetLastError(); cur = -2; }
+        const size_t row = (size_t)c->thumb_tw * (size_t)c->thumb_c, first = (size_t)c->thumb_lo * row, n = (size_t)(c->thumb_hi - c->thumb_lo) * row;
+        tmp.resize(n);
+        hipError_t e = hipSetDevice(c->device);
+        if (e == hipSuccess) e = hipMemcpy(tmp.data(), c->d_thumb + first, n * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemsetAsync(c->d_thumb + first, 0, n * sizeof(unsigned long long), nullptr);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);        // the slots' streams do not wait for the default stream
+        if (e != hipSuccess) { if (!rc) rc = hip_fail(e, "thumbnail read-back", AVIFGPU_writErr); continue; }
+        c->thumb_lo = c->thumb_hi = 0;
+        if (sums && tw == c->thumb_tw && th == c->thumb_th) for (size_t k = 0; k < n; ++k) sums[first + k] += tmp[k];
+    }
+    if (cur >= 0) (void)hipSetDevice(cur);
+    return rc;
+}
 int wait_all_impl(bool discard_hist);
 }
 int wait_all() { return wait_all_impl(false); }
@@ -1050,7 +1107,9 @@ int wait_all_impl(bool discard_hist)
         if (c->err && !first) { first = c->err; snprintf(msg, sizeof(msg), "%s", c->err_msg); }
         c->err = 0; c->err_msg[0] = 0;
     }
-    const int hrc = collect_histograms(discard_hist || first != 0);
+    int hrc = collect_histograms(discard_hist || first != 0);
+    const int trc = collect_thumbnails(discard_hist || first != 0);
+    if (!hrc) hrc = trc;
     if (first) set_error(msg);
     return first ? first : hrc;
 }

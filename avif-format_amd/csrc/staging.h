@@ -57,6 +57,19 @@ int  hot_variant();
 int  histogram_for_call(const avifgpu_write_desc* d, int mem_kind, uint64_t** bins);
 uint64_t* histogram_host_bins(int* nbins);           // the calling thread's armed HOST counters, or nullptr
 
+// ---- thumbnail_kernels.hip: the box-average thumbnail of a save (avifgpu_thumbnail_attach) ---------------------------
+struct ThumbArm { uint64_t* sums; int tw, th; };     // sums == nullptr: nothing armed
+// The calling thread's arming for a write of `mem_kind`: 0 and *arm, or formatBadParameters with a message when the memory kind
+// disagrees or the geometry does not admit the armed size (tw / th above the smallest used plane's width / height).
+int  thumbnail_for_call(const avifgpu_write_desc* d, const WriteGeom& g, int mem_kind, ThumbArm* arm);
+uint64_t* thumbnail_host_sums(int* tw, int* th);     // the calling thread's armed HOST sums, or nullptr
+// thumbnail rows [ty_lo, ty_hi) that source rows [row0, row0 + nrows) add to, over all planes
+void thumbnail_rows_of_tile(const avifgpu_write_desc* d, const WriteGeom& g, int row0, int nrows, int th, int& ty_lo, int& ty_hi);
+// Sum the output codes of one tile into sums[(ty * tw + tx) * planes + c], enqueued behind the tile's launch_write(): `planes` / `stride` are
+// the pointers that kernel wrote through (at row row0; chroma: row0 >> ys), sums lives on the stream's device.
+hipError_t launch_thumbnail(const avifgpu_write_desc* d, const WriteGeom& g, int row0, int nrows, const uint8_t* const planes[4],
+                            const int64_t stride[4], int tw, int th, unsigned long long* sums, hipStream_t st, int twin = 0);   // twin: avifgpu_probe_thumbnail
+
 // ---- write_kernels.hip / read_kernels.hip ---------------------------------------------------------------------------
 hipError_t launch_write(const WriteParams& p, int depth, int planes, bool dst16, int output, int xs, int ys,
                         int variant, hipStream_t st, char* label);

@@ -351,6 +351,49 @@ int32_t avifgpu_light_level_from_histogram(const uint64_t* bins, int32_t bit_dep
  * atomics-free / math-free twin for attribution (RGB, PQ, no profile, 16-byte aligned rows; the counts they leave are meaningless). */
 int32_t avifgpu_probe_histogram(const avifgpu_write_desc* desc, int32_t twin, const void* src, int64_t src_row_bytes, uint64_t* bins, void* stream);
 
+/* ---- thumbnail of a save: box average of the output codes ----------------------------------------------------------------------
+ * An extension: the reference declares fmtCannotCreateThumbnail and writes no thumbnail.  The statistic is taken from the OUTPUT of a
+ * save -- the planes the conversion kernel has just written -- by a kernel of its own behind the conversion of the same rows, so it
+ * is the same for every document depth, transfer, profile and output form, and the thumbnail is in exactly the colour representation
+ * of the main image.  Every CHANNEL of the output is reduced on its own: a channel is one plane of pw x ph samples, or one of the
+ * `planes` interleaved channels of plane 0 of a colour save in AVIFGPU_OUT_REFERENCE form; 4:2:x chroma planes are reduced from their
+ * own (W + xs) >> xs by (H + ys) >> ys.  Sample (x, y) of a channel belongs to cell (floor(x tw / pw), floor(y th / ph)), and
+ *     sums[(ty * tw + tx) * C + c] += code,      C = desc->planes, c in output order R,G,B[,A] | Y[,A] | Y,Cb,Cr[,A].
+ * Integer sums add in any order: they are the same for every tiling, every number of bound devices, every launch shape, pinned or
+ * pageable memory, HOST or DEVICE pointers.  Alpha is averaged like any channel and colour is the plain mean of the codes: right for
+ * premultiplied saves, and for straight alpha what every plain scaler does.  ALPHA-WEIGHTED COLOUR MEANS ARE NOT COMPUTED.
+ *
+ * Arm (sums != NULL) or disarm (NULL: always succeeds) the calling thread.  1 <= tw, th <= 1024, else formatBadParameters.  sums holds
+ * tw * th * planes counters (4 * tw * th is always enough) and is never zeroed by the library.  While armed, every avifgpu_write_rows*
+ * call of this thread, at any depth, adds its rows' output codes; reads are unaffected.  The FormatRecord shim's saves run on the
+ * caller's thread and honour it with mem_kind HOST, all tiles of a save summed.  mem_kind says where sums live and must equal the
+ * mem_kind of the calls: HOST -- the sums are complete when each call returns (a call that fails adds nothing); DEVICE -- the adds are
+ * enqueued on the call's stream behind its kernel, they read the caller's dst planes.  A call whose mem_kind differs, or whose
+ * smallest used plane is narrower than tw or lower than th, fails with formatBadParameters before anything is launched or queued.  A
+ * code histogram may be armed at the same time.  Host-only bookkeeping: needs no device. */
+int32_t avifgpu_thumbnail_attach(uint64_t* sums, int32_t tw, int32_t th, int32_t mem_kind);
+
+/* Host only.  The size an aspect-preserving fit of the image into a bbox x bbox square gives: the image's own size when
+ * max(W, H) <= bbox; otherwise the longer side becomes bbox and the other max(1, (2 other bbox + longer) / (2 longer)).  Both are then
+ * clamped to the smallest used plane's width and height (so that avifgpu_thumbnail_attach + the save accept them) and to 1024.
+ * bbox < 1, a null argument or an invalid desc is formatBadParameters. */
+int32_t avifgpu_thumbnail_fit(const avifgpu_write_desc* desc, int32_t bbox, int32_t* tw, int32_t* th);
+
+/* Host only, integer arithmetic.  The thumbnail code of a cell is floor((2 sum + n) / (2 n)), n = the cell's sample count in that plane,
+ * taken from the geometry: n = (ceil((tx + 1) pw / tw) - ceil(tx pw / tw)) * (the same in y).  Written in the form of the main output at
+ * tw x th: plane 0 interleaved for a colour REFERENCE save; Y (+ plane 3 = A) for gray; Y, Cb, Cr (+ A) planes, always 4:4:4, for YCBCR
+ * output.  Samples are u8 at bit depth 8, little-endian u16 otherwise; dst_stride in bytes.  formatBadParameters when a sum exceeds
+ * n * (2^bit_depth - 1) -- the caller did not feed a whole frame exactly once -- and then nothing is written. */
+int32_t avifgpu_thumbnail_from_sums(const avifgpu_write_desc* desc, int32_t tw, int32_t th, const uint64_t* sums,
+                                    void* const dst[4], const int64_t dst_stride[4]);
+
+/* Measuring aid (tools/bench_thumbnail.py): launch the thumbnail kernel ALONE on the whole frame's output planes at device pointers
+ * `planes` (as avifgpu_write_rows wrote them: the same plane use, strides in bytes), into device sums, on `stream`.  twin 0 = the kernel
+ * itself (the same sums an armed avifgpu_write_rows adds); 1 = its atomics-free twin for attribution (the loads and the register adds
+ * only: sums is left alone). */
+int32_t avifgpu_probe_thumbnail(const avifgpu_write_desc* desc, int32_t twin, int32_t tw, int32_t th, const void* const planes[4],
+                                const int64_t stride[4], uint64_t* sums, void* stream);
+
 /*
  * Inverse direction.  src[i] / src_stride[i] are what heif_image_get_plane_readonly returns
  * (ReadHeifImage.cpp:104-111) advanced to row `row0` (chroma: row0 >> yShift); plane order is
