@@ -174,7 +174,7 @@ def oracle_write(desc, src, row0=0, nrows=None, stride_pad=0, return_raw=False):
     return bufs if return_raw else _trim(desc, bufs, nrows, write_planes)
 
 
-def gpu_write(gpu, desc, src, row0=0, nrows=None, mem="device", stride_pad=0, return_raw=False):
+def gpu_write(gpu, desc, src, row0=0, nrows=None, mem="device", stride_pad=0, return_raw=False, icc=None):
     nrows = desc.height - row0 if nrows is None else nrows
     bufs = _alloc_write_out(desc, nrows, stride_pad)
     tile = src[row0:row0 + nrows]
@@ -182,7 +182,7 @@ def gpu_write(gpu, desc, src, row0=0, nrows=None, mem="device", stride_pad=0, re
         ptrs = [bufs[i].ctypes.data if i in bufs else None for i in range(4)]
         strides = [bufs[i].strides[0] if i in bufs else 0 for i in range(4)]
         gpu.write_rows(desc, row0, nrows, tile.ctypes.data if nrows else src.ctypes.data, src.strides[0], ptrs, strides,
-                       mem=pkg.MEM_HOST)
+                       mem=pkg.MEM_HOST, icc=icc)
     else:
         import torch
         dev = f"cuda:{gpu.device}"
@@ -193,7 +193,7 @@ def gpu_write(gpu, desc, src, row0=0, nrows=None, mem="device", stride_pad=0, re
         strides = [bufs[i].strides[0] if i in bufs else 0 for i in range(4)]
         stream = torch.cuda.current_stream(dev).cuda_stream
         gpu.write_rows(desc, row0, nrows, d_src.data_ptr(), src.strides[0], ptrs, strides, mem=pkg.MEM_DEVICE,
-                       stream=stream)
+                       stream=stream, icc=icc)
         torch.cuda.synchronize(dev)
         for pl in bufs:
             bufs[pl] = d_out[pl].cpu().numpy().view(bufs[pl].dtype).reshape(bufs[pl].shape)

@@ -14,6 +14,39 @@ Bands (codes):
    from float64 is at most 1.2e-7 relative (HLG) and 1.0e-7 (428), i.e. at most 5e-4 codes at 12 bit.  The band is the
    kernels' stated EOTF bar for the same curves (tests/test_gpu_t2_truth.py: 2e-6 relative), 17x the oracle's own deviation,
    so a v_log/v_exp evaluation of a few ulps fits and a wrong constant does not.
+
+Behind a document profile.  A 32-bit save behind an ICC stage (avifgpu_icc_transform, avifgpu_icc_sampled32) runs the curve on
+the stage's float32 output, which two evaluations produce: lcms2's float pipeline (the reference converts the row in place, then
+runs the pixel loop) and the kernels'.  The truth of the stage is computable from the prepared struct alone: t_j = curve_j(x_j) in
+float64 (a parametric channel as DefaultEvalParametricFn has it; a sampled channel as curve[j][word], word the exact integer
+_cmsQuickSaturateWord(x * 65535.0), magic-number floor included), v_i = sum_j m_ij t_j, and w_i = inverse type-4 curve(v_i) for the
+sRGB target.  A sample is determined when every float32 within +-dv of that value gives one code: the ends go through the
+premultiply (clamp and a float32 product: monotone) and the curve, each end is widened by the curve's band above (Clip has no
+curve: the absolute part alone), and both must truncate to the same code or sit beyond the same clamped end.  dv is the larger of
+two half-widths, in units of u = 2^-24 (S_i = sum_j |m_ij| |t_j|, slope_i = the inverse curve's derivative at v_i):
+ * lcms2: 4 u S_i (Rec.2020 target), 4 u (slope_i S_i + |w_i|) (sRGB target).  Measured on 400 000 pixels per profile and target
+   (tests/test_truth64_icc.py): at most 1.96 and 1.29 of those units -- the float between its stages and the float it returns -- so
+   the 4 is a margin of 2x.
+ * the kernels, from their arithmetic as it stands in csrc/write_kernels.hip:
+     - the 3x3 in float32 (AG_ICC_MATRIX_F32; icc_apply_f, icc_apply_sampled, the streaming kernels): each coefficient is rounded
+       once on the host, the first product and the two FMAs round once each, every one of them bounded by u S_i: 4 u S_i.  (The
+       generic icc = 1 kernel accumulates in double and rounds once: inside this.)
+     - a linear channel (gamma 1) is skipped and a sampled channel is the tabulated float itself (LDS and memory forms return
+       curve[][] bit for bit, tests/test_gpu_icc.py): no error of their own.
+     - a parametric channel, icc_trc_f / icc_trc_simple with AG_ICC_FASTPOW: lin = fma(a, R, b) on the rounded a and b -- u |a R|,
+       u |b| (each only where the float copy is inexact) and u |lin| for the operation, which x^g multiplies by g -- then
+       exp2(g * log2(lin)): with e = g log2(lin), the error of v_log_f32, the rounded g and the rounded product act on e, the error
+       of v_exp_f32 on the result: relative ((L + [g inexact] + 1) |e| ln 2 + E) u.  A function of the sample, not a constant: for
+       |e| = 30 it is 7e-6.  The "+ add" of types 3 and 5 adds u |add| and u |t|; the linear segment c R + f adds u for each
+       inexact coefficient and one for the FMA.  These reach v_i through the matrix as sum_j |m_ij| err_j.
+     - icc_inv4_f, the sRGB target: slope_i times all of the above, then the same pow bound on v^(1/g), u |b| and u |pow - b| for
+       the subtraction, divided by a, and 2 u |w| for the rounded 1/a and its product; below the break 2 u |w|.
+   L and E: neither this repository nor the hardware guides state the accuracy of v_log_f32 / v_exp_f32.  The source comments of
+   write_kernels.hip assume 1 ulp each, i.e. 2 u relative; taken here with a margin of 2x, L = E = 4.  This is an ASSUMPTION, held by
+   the measurement of tests/test_gpu_icc_determined.py::test_icc_write_mismatches_use_at_most_the_band (the share of the band the
+   kernels use on undrawn sources, profiles/icc_truth/band_usage.txt), not a measured bound.
+ The kernels compare R with the float copy of a curve's break point and the truth with the double: they differ for the one float
+ between the two at most, where both segments agree to 1e-8 (far inside BAND_ABS).
 """
 from __future__ import annotations
 
@@ -70,6 +103,33 @@ class _Ops:
 
     def sqrt(self, x):
         return self.m.sqrt(x) if self.t else np.sqrt(x)
+
+    def abs(self, x):
+        return x.abs() if self.t else np.abs(x)
+
+    def log2(self, x):
+        return self.m.log2(x) if self.t else np.log2(x)
+
+    def floor(self, x):
+        return x.floor() if self.t else np.floor(x)
+
+    def clip(self, x, lo, hi):
+        return x.clamp(lo, hi) if self.t else np.clip(x, lo, hi)
+
+    def max2(self, a, b):
+        return self.m.maximum(a, b) if self.t else np.maximum(a, b)
+
+    def f32(self, x):
+        return x.to(self.m.float32) if self.t else np.asarray(x).astype(np.float32)
+
+    def stack(self, xs):
+        return self.m.stack(xs, -1) if self.t else np.stack(xs, -1)
+
+    def lookup(self, table, idx):
+        """table[idx] for a numpy table and an integer-valued float index array of either kind."""
+        if self.t:
+            return self.m.from_numpy(np.ascontiguousarray(table)).to(idx.device)[idx.to(self.m.int64)]
+        return table[idx.astype(np.int64)]
 
 
 # ---- OETFs (write direction) -------------------------------------------------------------------------------------------------
@@ -262,3 +322,241 @@ def output_masks(desc, pix, xp=np):
     out[1] = c
     out[2] = c
     return out
+
+
+# ---- the ICC stage of a 32-bit save behind a document profile (docstring: "Behind a document profile") -----------------------------
+ICC_LCMS_UNITS = 4.0          # lcms2's float pipeline: measured <= 1.93 (Rec.2020 target) and <= 1.33 (sRGB target) units, doubled
+ICC_MATRIX_UNITS = 4.0        # the kernels' fp32 3x3: one rounded coefficient and three rounded operations per row, on sum |m||t|
+ICC_LOG_UNITS = 4.0           # v_log_f32: 1 ulp = 2 units of 2^-24 relative (ASSUMED, see the docstring), doubled
+ICC_EXP_UNITS = 4.0           # v_exp_f32: likewise
+ICC_TOL = 0.0001              # lcms2's MATRIX_DET_TOLERANCE, as DefaultEvalParametricFn uses it
+_QUICK_FLOOR_MAGIC = 68719476736.0 * 1.5
+
+
+def _icc_base(xf):
+    return xf.base if hasattr(xf, "parametric_mask") else xf
+
+
+def _inexact(x):
+    """1.0 where the kernels' float copy of a double parameter is a rounded one, else 0.0."""
+    return 0.0 if float(f32(x)) == float(x) else 1.0
+
+
+def icc_channel_is_sampled(xf, c):
+    return hasattr(xf, "parametric_mask") and not (xf.parametric_mask >> c) & 1
+
+
+def icc_has_nonlinear_parametric(xf):
+    b = _icc_base(xf)
+    return any(not icc_channel_is_sampled(xf, c) and not (b.trc_type[c] == 1 and b.trc_params[c][0] == 1.0) for c in range(3))
+
+
+def quick_saturate_word64(v):
+    """lcms2's _cmsQuickSaturateWord(v * 65535.0) of float32 samples (cmsgamma.c: the word a sampled curve is entered with), as an
+    integer-valued float64 array: the product and the + 0.5 in double, the magic-number floor of _cmsQuickFloor -- the addition of
+    1.5 * 2^36 rounds the value to 2^-16, the library then shifts the low word right by 16, i.e. takes the floor -- and the two
+    saturation tests."""
+    o = _Ops(v)
+    d = o.f64(v) * 65535.0 + 0.5
+    x = o.clip(d, 0.0, 65535.0) - 32767.0
+    w = o.floor((x + _QUICK_FLOOR_MAGIC) - _QUICK_FLOOR_MAGIC) + 32767.0
+    return o.where(d <= 0.0, 0.0 * d, o.where(d >= 65535.0, 0.0 * d + 65535.0, w))
+
+
+def _pow_units(o, ex, inexact_g):
+    """Relative error, in units of 2^-24, of exp2(g * log2(x)) as icc_pow32 evaluates it (AG_ICC_FASTPOW), ex = g log2 x: the
+    error of v_log_f32, the rounded exponent g and the rounded product all act on ex, v_exp_f32 on the result."""
+    return (ICC_LOG_UNITS + inexact_g + 1.0) * o.abs(ex) * float(np.log(2.0)) + ICC_EXP_UNITS
+
+
+def _trc64(o, typ, P, R):
+    """(t, err): one lcms2 parametric curve (types 1-5, DefaultEvalParametricFn as eval_parametric in csrc/icc_profile.cpp restates
+    it) of the float64 samples R, and the bound of icc_trc_f's / icc_trc_simple's absolute error on it in units of 2^-24."""
+    g, a, b, c, d, e, f = (float(P[k]) for k in range(7))
+    zero = 0.0 * R
+    if typ == 1:
+        if g == 1.0:                                               # the kernels skip the curve (icc_trc_linear): t = R, exactly
+            return R + zero, zero
+        up, a, b, add, nonpos = R >= 0, 1.0, 0.0, 0.0, 0.0
+        lc, lf = (1.0 if abs(g - 1.0) < ICC_TOL else 0.0), 0.0
+    elif typ in (2, 3):
+        if abs(a) < ICC_TOL:
+            return zero, zero
+        disc = -b / a
+        add, nonpos = (c, 0.0) if typ == 3 else (0.0, 0.0)
+        up = R >= (max(disc, 0.0) if typ == 3 else disc)
+        lc, lf = 0.0, add
+    elif typ == 4:
+        up, add, nonpos, lc, lf = R >= d, 0.0, 0.0, c, 0.0
+    elif typ == 5:
+        up, add, nonpos, lc, lf = R >= d, e, e, c, f
+    else:
+        raise ValueError(f"parametric curve type {typ}")
+    lin = a * R + b
+    pos = lin > 0
+    safe = o.where(pos, lin, zero + 1.0)
+    pw = o.where(pos, o.pow(safe, g), zero)
+    hi = o.where(pos, pw + add, zero + nonpos)
+    low = lc * R + lf
+    # lin = fma(a, R, b) on the rounded a and b: one unit each where they are rounded, one for the operation; x^g multiplies it by g
+    lin_units = (_inexact(a) * o.abs(a * R) + _inexact(b) * abs(b)) / o.abs(safe) + (0.0 if (a == 1.0 and b == 0.0) else 1.0)
+    hi_err = pw * (abs(g) * lin_units + _pow_units(o, g * o.log2(safe), _inexact(g)))
+    if add != 0.0:
+        hi_err = hi_err + _inexact(add) * abs(add) + o.abs(hi)
+    low_err = _inexact(lc) * o.abs(lc * R) + _inexact(lf) * abs(lf)
+    if not (lc in (0.0, 1.0) and lf == 0.0):
+        low_err = low_err + o.abs(low)
+    return o.where(up, hi, low), o.where(up, o.where(pos, hi_err, zero), low_err + zero)
+
+
+def _inv4_64(o, P, v):
+    """(w, slope, err): the inverse of lcms2's parametric type 4 (type -4, the curve in front of an sRGB destination), its
+    derivative, and the bound of icc_inv4_f's absolute error in units of 2^-24.  P = out_params."""
+    g, a, b, c, brk, ig = float(P[0]), float(P[1]), float(P[2]), float(P[3]), float(P[5]), float(P[6])
+    zero = 0.0 * v
+    up = v >= brk
+    safe = o.where(up, v, zero + 1.0)
+    if abs(g) < ICC_TOL or abs(a) < ICC_TOL:
+        hi, hs, he = zero, zero, zero
+    else:
+        pw = o.pow(safe, 1.0 / g)
+        hi = (pw - b) / a
+        hs = pw / (g * a * safe)
+        # pow, the subtraction of the rounded b, the product with the rounded 1/a
+        he = (pw * _pow_units(o, ig * o.log2(safe), _inexact(ig)) + _inexact(b) * abs(b) + o.abs(pw - b)) / abs(a) + 2.0 * o.abs(hi)
+    if abs(c) < ICC_TOL:
+        lo, ls, le = zero, zero, zero
+    else:
+        lo, ls = v / c, zero + 1.0 / c
+        le = 2.0 * o.abs(lo)                                       # the rounded 1/c and the product
+    return o.where(up, hi, lo), o.where(up, hs, ls), o.where(up, he, le)
+
+
+def _icc_eval(xf, col):
+    """Everything of the stage at once.  col: (..., 3) float32 samples (numpy or torch).  Returns a dict of (..., 3) float64 arrays:
+    value (the stage's output), mag (sum_j |m_ij| |t_j|), slope (of the inverse curve; ones for the Rec.2020 target), lcms and kernel
+    (the two evaluations' error bounds, in units of 2^-24)."""
+    o = _Ops(col)
+    base = _icc_base(xf)
+    R = o.f64(col)
+    ts, es = [], []
+    for ch in range(3):
+        if icc_channel_is_sampled(xf, ch):
+            word = quick_saturate_word64(col[..., ch])
+            ts.append(o.f64(o.lookup(np.ctypeslib.as_array(xf.curve)[ch], word)))      # the tabulated float, exactly: no error of its own
+            es.append(0.0 * R[..., ch])
+        else:
+            t, e = _trc64(o, int(base.trc_type[ch]), base.trc_params[ch], R[..., ch])
+            ts.append(t)
+            es.append(e)
+    m = [float(x) for x in base.matrix]
+    v, mag, prop = [], [], []
+    for i in range(3):
+        v.append(sum(m[3 * i + j] * ts[j] for j in range(3)))
+        mag.append(sum(abs(m[3 * i + j]) * o.abs(ts[j]) for j in range(3)))
+        prop.append(sum(abs(m[3 * i + j]) * es[j] for j in range(3)))
+    v, mag, prop = o.stack(v), o.stack(mag), o.stack(prop)
+    kernel = ICC_MATRIX_UNITS * mag + prop
+    if base.out_curve == 4:
+        w, slope, inv_err = _inv4_64(o, base.out_params, v)
+        return dict(value=w, mag=mag, slope=slope, lcms=ICC_LCMS_UNITS * (slope * mag + o.abs(w)), kernel=slope * kernel + inv_err)
+    return dict(value=v, mag=mag, slope=0.0 * v + 1.0, lcms=ICC_LCMS_UNITS * mag, kernel=kernel)
+
+
+def icc_stage64(xf, col):
+    """(value, mag, slope): float64 truth of the ICC stage -- avifgpu_icc_transform (parametric types 1-5, both targets) and
+    avifgpu_icc_sampled32 (sampled channels through the exact 16-bit word and curve[c][word]; mixed profiles by parametric_mask) --
+    of (..., 3) float32 samples; mag = sum_j |m_ij| |t_j|; slope = the inverse curve's derivative at the matrix output (sRGB target),
+    None for the Rec.2020 target."""
+    r = _icc_eval(xf, col)
+    return r["value"], r["mag"], (r["slope"] if _icc_base(xf).out_curve == 4 else None)
+
+
+def icc_lcms_unit(xf, col):
+    """The unit lcms2's deviation is measured in: 2^-24 * sum |m||t| (Rec.2020 target), 2^-24 * (slope * sum |m||t| + |w|) (sRGB)."""
+    r = _icc_eval(xf, col)
+    return U32 * r["lcms"] / ICC_LCMS_UNITS
+
+
+def icc_band(xf, col):
+    """Per-sample half-width dv of the stage's output: both judged evaluations -- lcms2's float pipeline and the kernels' -- lie
+    within value +- dv (docstring)."""
+    r = _icc_eval(xf, col)
+    return U32 * _Ops(col).max2(r["lcms"], r["kernel"])
+
+
+def icc_truth_rows(desc, xf, src):
+    """src with every pixel's R, G, B replaced by float32(truth): what lcms2's in-place row conversion leaves, alpha untouched."""
+    px = src.reshape(src.shape[0], desc.width, desc.planes).copy()
+    px[..., :3] = icc_stage64(xf, px[..., :3])[0].astype(np.float32)
+    return np.ascontiguousarray(px.reshape(src.shape))
+
+
+def _curve_codes64(desc, x):
+    """(t, w): float64 code of float32 pre-curve values and the curve band's half-width there.  Clip has no curve: BAND_ABS alone."""
+    o = _Ops(x)
+    maxv = float((1 << desc.bit_depth) - 1)
+    if desc.transfer == pkg.TRANSFER_CLIP:
+        t = o.f64(x) * maxv
+        return t, 0.0 * t + BAND_ABS
+    t = oetf64(desc, x) * maxv
+    return t, band_rel(desc) * o.relu(t) + BAND_ABS
+
+
+def icc_code_interval(desc, xf, px, parts=False):
+    """(t, lo, hi), each (..., 3) float64 codes (unclamped): the truth and the ends of everything either evaluation may give.  px:
+    (..., planes) float32 pixels, 3 or 4 planes.  The reference converts the row first and runs the pixel loop on the converted row,
+    so the premultiply clamp(c) * a acts on the stage's float32 output: any float32 inside [v - dv, v + dv] lies between the two
+    rounded ends, and clamp, the float32 product and the curves are monotone, so the interval goes through them end by end.
+    parts: also the two ends before the curve's band widens them, i.e. what dv alone makes of the interval."""
+    o = _Ops(px)
+    col = px[..., :3]
+    r = _icc_eval(xf, col)
+    dv = U32 * o.max2(r["lcms"], r["kernel"])
+    ends = [o.f32(r["value"]), o.f32(r["value"] - dv), o.f32(r["value"] + dv)]
+    if desc.planes == 4 and desc.alpha_state == pkg.ALPHA_PREMULTIPLIED:
+        a = o.clip(px[..., 3:], 0.0, 1.0)                          # float32, as stage_a_values
+        for k, x in enumerate(ends):
+            pre = o.clip(x, 0.0, 1.0) * a
+            pre = o.where(a == 0, 0.0 * pre, pre)
+            ends[k] = o.where(a < 1.0, pre, x)
+    (t, _), (tl, wl), (th, wh) = (_curve_codes64(desc, x) for x in ends)
+    return (t, tl - wl, th + wh, tl, th) if parts else (t, tl - wl, th + wh)
+
+
+def determined_codes_icc(desc, xf, src):
+    """(codes, mask), both (H, W, 3): the float64 code of every colour sample of a 32-bit save behind the ICC stage xf
+    (avifgpu_icc_transform or avifgpu_icc_sampled32), and whether it is determined: both ends of the interval truncate to the same
+    code, or both sit at or beyond the same clamped end.  Alpha is copied by the transform: alpha_codes() as before."""
+    o = _Ops(src)
+    maxv = float((1 << desc.bit_depth) - 1)
+    t, lo, hi = icc_code_interval(desc, xf, src.reshape(src.shape[0], desc.width, desc.planes))
+    ql, qh = o.floor(o.clip(lo, 0.0, maxv)), o.floor(o.clip(hi, 0.0, maxv))
+    codes = o.floor(o.clip(t, 0.0, maxv))
+    return (codes if o.t else codes.astype(np.int64)), ql == qh
+
+
+def make_determined_source_icc(desc, xf, seed=harness.SEED, max_rounds=400):
+    """harness.make_write_source -- with abs() where the profile has a non-linear parametric channel, as the ICC tests draw it: no
+    lcms2 build is asked about negative inputs of a power law -- with every PIXEL that has an undetermined colour sample drawn again
+    (the matrix mixes the channels) until none is left.  Returns (src, replaced), replaced counting pixels, with repeats."""
+    nonneg = icc_has_nonlinear_parametric(xf)
+    src = harness.make_write_source(desc, seed=seed)
+    px = src.reshape(desc.height, desc.width, desc.planes)
+    if nonneg:
+        px[..., :3] = np.abs(px[..., :3])
+    rng = np.random.default_rng(seed + 0x1CC)
+    maxv = float((1 << desc.bit_depth) - 1)
+    flat = px.reshape(-1, desc.planes)
+    todo = np.arange(flat.shape[0])
+    replaced = 0
+    for _ in range(max_rounds):
+        _, lo, hi = icc_code_interval(desc, xf, flat[todo])
+        bad = ~(np.floor(np.clip(lo, 0.0, maxv)) == np.floor(np.clip(hi, 0.0, maxv))).all(axis=-1)
+        todo = todo[bad]
+        if todo.size == 0:
+            return src, replaced
+        replaced += todo.size
+        c = _draw_colour(rng, todo.size * 3).reshape(-1, 3)
+        flat[todo, :3] = np.abs(c) if nonneg else c
+    raise AssertionError(f"{desc.width}x{desc.height}: pixels still undetermined after {max_rounds} rounds")
