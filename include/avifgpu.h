@@ -182,7 +182,9 @@ enum {
 typedef struct avifgpu_write_desc {
     int32_t width;               /* imageSize.h */
     int32_t height;              /* imageSize.v */
-    int32_t depth;               /* formatRecord->depth: 8, 16 (0..32768), 32 (float) */
+    int32_t depth;               /* formatRecord->depth: 8, 16 (0..32768), 32 (float).  Samples outside that are DEFINED (the reference's
+                                  * behaviour is not): a 16-bit sample above 32768 -- alpha included -- counts as 32768, in front of
+                                  * the ICC stage as well; a 32-bit NaN saves as code 0, +-Inf as code 0 or the maximum code. */
     int32_t planes;              /* formatRecord->planes: 1|2 gray(+A), 3|4 RGB(+A); alpha last */
     int32_t bit_depth;           /* saveOptions.imageBitDepth as 8 | 10 | 12 */
     int32_t transfer;            /* saveOptions.hdrTransferFunction (depth 32 only), AVIFGPU_TRANSFER_* */
@@ -209,7 +211,10 @@ typedef struct avifgpu_read_desc {
     int32_t height;
     int32_t colorspace;          /* heif_image_get_colorspace: AVIFGPU_COLORSPACE_* */
     int32_t chroma;              /* heif_image_get_chroma_format: AVIFGPU_CHROMA_* (YCbCr only) */
-    int32_t bit_depth;           /* heif_image_get_bits_per_pixel_range(Y or R): 8 | 10 | 12 | 16 */
+    int32_t bit_depth;           /* heif_image_get_bits_per_pixel_range(Y or R): 8 | 10 | 12 | 16.  A 10- / 12-bit sample above
+                                  * 2^bit_depth - 1 in its 16-bit container is DEFINED: planar RGB (and its alpha) opened at depth 16
+                                  * keeps the low bit_depth bits (mask), opened at depth 32 counts as 2^bit_depth - 1 (clamp); YCbCr
+                                  * and monochrome planes and their alpha clamp at every depth. */
     int32_t depth;               /* host depth the driver chose (Read.cpp:359-515): 8 | 16 | 32 */
     int32_t alpha_state;         /* AVIFGPU_ALPHA_* (Read.cpp:155-172) */
     int32_t has_nclx;            /* 0 => nclxProfile == nullptr (BT.601, full range defaults) */

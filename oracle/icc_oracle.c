@@ -317,7 +317,9 @@ static uint16_t lcms_to_host(uint16_t i)
     return (uint16_t)(v < 0 ? 0 : (v > 32768 ? 32768 : v));
 }
 /* raw != 0: plain lcms2 16-bit transform on [0, 65535] data (used to pin the CLUT restatement); raw == 0: the reference flow.
- * Samples above 32768 are outside Photoshop's range (the reference would index past its table): callers do not pass them. */
+ * Samples above 32768 are outside Photoshop's range (the reference would index past its table): host_to_lcms saturates at 65535,
+ * which is what 32768 maps to, so such a sample counts as 32768 -- the rule of avif_oracle.c for every 16-bit sample
+ * (tests/test_out_of_range.py::test_icc16_flow_clamps_its_input). */
 int32_t oracle_icc_convert_rows_to_srgb16(const void* icc, uint32_t icc_size, int32_t has_alpha, int32_t raw,
                                           void* rows, uint32_t width, uint32_t nrows, uint32_t row_bytes)
 {

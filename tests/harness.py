@@ -138,6 +138,100 @@ def make_read_source(desc, seed=SEED, stride_pad=0):
     return out
 
 
+WRITE_OVER_SPECIALS = (32769, 0x8001, 0xFFFE, 0xFFFF)         # just past Photoshop's white (twice over: decimal and hex), the top two
+WRITE_OVER_KINDS_ALPHA = ("all-over", "colour-over-alpha-0", "colour-over-alpha-mid", "colour-over-alpha-white",
+                          "alpha-over-colour-in", "alpha-over-colour-over")
+WRITE_OVER_KINDS_OPAQUE = ("all-over",)
+
+
+def write_over_range_kinds(px, has_alpha):
+    """{kind: bool mask over the pixels of px (N, planes)} -- the whole-pixel kinds make_write_source_over_range plants."""
+    over = px > 32768
+    if not has_alpha:
+        return {"all-over": over.all(axis=1)}
+    col, al = over[:, :-1].all(axis=1), px[:, -1]
+    return {"all-over": over.all(axis=1),
+            "colour-over-alpha-0": col & (al == 0), "colour-over-alpha-mid": col & (al == 16384),
+            "colour-over-alpha-white": col & (al == 32768),
+            "alpha-over-colour-in": (al > 32768) & ~over[:, :-1].any(axis=1),
+            "alpha-over-colour-over": (al > 32768) & col}
+
+
+def make_write_source_over_range(desc, seed=SEED, share=0.2):
+    """make_write_source for a 16-bit document with `share` of ALL samples (alpha included) redrawn from (32768, 65535] -- the
+    inputs oracle/avif_oracle.c:31-33 defines as 32768 -- plus the special values and whole pixels of every kind above, once at
+    the start of the frame and (frames of 64 pixels and more) once more at the end of the last row, where the ragged lanes are.
+    Asserts that every channel holds an over-range sample and, from 16 pixels on, that every special and every kind is present."""
+    assert desc.depth == 16, "Photoshop's 16-bit range is what has an upper end below the container's"
+    H, W, P = desc.height, desc.width, desc.planes
+    has_alpha = P in (2, 4)
+    ncol = P - 1 if has_alpha else P
+    N = H * W
+    a = make_write_source(desc, seed).reshape(H, W, P).copy()
+    rng = np.random.default_rng([seed, 0x0fe2])
+    m = rng.random((H, W, P)) < share
+    a[m] = rng.integers(32769, 65536, size=int(m.sum())).astype(np.uint16)
+    px = a.reshape(N, P)
+    kinds = WRITE_OVER_KINDS_ALPHA if has_alpha else WRITE_OVER_KINDS_OPAQUE
+    base = len(kinds)
+    for j, v in enumerate(WRITE_OVER_SPECIALS):                          # one special per pixel and channel (small frames wrap round)
+        for k in range(P):
+            px[(base + j * P + k) % N, k] = v
+
+    def plant(at):
+        over = rng.integers(32770, 65535, size=(len(kinds), ncol)).astype(np.uint16)
+        inside = rng.integers(0, 32769, size=ncol).astype(np.uint16)
+        for i, kind in enumerate(kinds):
+            p = px[at(i)]
+            if kind == "all-over":
+                p[:] = 0xFFFF
+            elif kind == "alpha-over-colour-in":
+                p[:ncol], p[-1] = inside, 40000
+            elif kind == "alpha-over-colour-over":
+                p[:ncol], p[-1] = 32769, 0xFFFE
+            else:
+                p[:ncol] = over[i]
+                p[-1] = {"colour-over-alpha-0": 0, "colour-over-alpha-mid": 16384, "colour-over-alpha-white": 32768}[kind]
+    if N >= 16:
+        plant(lambda i: i)
+    if N >= 64:
+        plant(lambda i: N - 1 - i)
+    assert (px > 32768).any(axis=0).all(), "a channel without an over-range sample"
+    if N >= 16:
+        assert all((px == v).any() for v in WRITE_OVER_SPECIALS), "a special value is missing"
+        present = write_over_range_kinds(px, has_alpha)
+        assert all(present[k].any() for k in kinds), [k for k in kinds if not present[k].any()]
+    return np.ascontiguousarray(a.reshape(H, W * P))
+
+
+def make_read_source_over_range(desc, seed=SEED, share=0.1, stride_pad=0):
+    """make_read_source for 10- / 12-bit planes in their 16-bit containers with `share` of EVERY plane's samples redrawn from
+    (maxc, 65535] -- masked by a 16-bit planar-RGB open, clamped by every other one (oracle/avif_oracle.c:34-35) -- plus
+    maxc + 1, 0x8000, 0x8001 and 0xFFFF at the start of each plane and (planes of 64 samples and more) at the end of the last row.
+    Asserts that every plane holds an over-range sample and, from 16 samples on, each of the four values."""
+    assert desc.bit_depth in (10, 12), "8-bit planes fill their container; 16-bit ones too"
+    maxc = (1 << desc.bit_depth) - 1
+    specials = (maxc + 1, 0x8000, 0x8000 | 1, 0xFFFF)
+    out = make_read_source(desc, seed, stride_pad)
+    rng = np.random.default_rng([seed, 0x0fe3])
+    for pl, (w, xs, ys) in read_planes(desc).items():
+        arr = out[pl]
+        h = arr.shape[0]
+        body = arr[:, :w]
+        m = rng.random((h, w)) < share
+        body[m] = rng.integers(maxc + 1, 65536, size=int(m.sum())).astype(np.uint16)
+        n = h * w
+        for j, v in enumerate(specials):
+            body[(j % n) // w, (j % n) % w] = v
+            if n >= 64:
+                body[h - 1, w - 1 - j] = v
+        assert (body > maxc).any(), (pl, "no over-range sample")
+        if n >= 16:
+            assert all((body == v).any() for v in specials), (pl, "a special value is missing")
+        assert not arr[:, w:].any()                                      # the padding of a plane row stays what make_read_source left
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # runners
 # ------------------------------------------------------------------------------------------------

@@ -59,7 +59,9 @@ def test_write_parity_host_buffers(gpu, cid, kw):
 
 
 def test_write_exhaustive_16bit_rescale(gpu):
-    """All 32769 Photoshop 16-bit codes through the 16->8/10/12 rescale (reference LUTs WriteHeifImage.cpp:114-166)."""
+    """All 32769 Photoshop 16-bit codes through the 16->8/10/12 rescale (reference LUTs WriteHeifImage.cpp:114-166) -- and all 65536 values
+    of the container: above 32768 the reference reads past its table, the oracle and the kernels count the sample as 32768
+    (oracle/avif_oracle.c:31-33), so those give the maximum code."""
     for bits in (8, 10, 12):
         d = pkg.WriteDesc(width=32769, height=1, depth=16, planes=1, bit_depth=bits, alpha_state=pkg.ALPHA_NONE,
                           output=pkg.OUT_REFERENCE)
@@ -67,6 +69,19 @@ def test_write_exhaustive_16bit_rescale(gpu):
         want = harness.oracle_write(d, src)
         got = harness.gpu_write(gpu, d, src)
         assert np.array_equal(got[0], want[0]), bits
+        dw = pkg.WriteDesc(width=65536, height=1, depth=16, planes=1, bit_depth=bits, alpha_state=pkg.ALPHA_NONE,
+                           output=pkg.OUT_REFERENCE)
+        wide = np.arange(65536, dtype=np.uint16).reshape(1, -1)
+        try:
+            for variant in (1 | 2 | 4, 0):                                # the elementwise streaming kernel, the generic one
+                gpu.lib.avifgpu_set_hot_variant(variant)
+                all_codes = harness.gpu_write(gpu, dw, wide)[0]
+                assert ("write_px" in gpu.last_kernel()) == (variant == 0), gpu.last_kernel()
+                assert np.array_equal(all_codes, harness.oracle_write(dw, wide)[0]), (bits, variant)
+                assert np.array_equal(all_codes[:, :32769], want[0]), (bits, variant)
+                assert np.all(all_codes[:, 32768:] == (1 << bits) - 1), (bits, variant)
+        finally:
+            gpu.lib.avifgpu_set_hot_variant(1 | 2 | 4)
 
 
 def test_write_exhaustive_premultiply_u8(gpu):
