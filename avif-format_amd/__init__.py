@@ -232,6 +232,13 @@ ABI = [
     ("avifgpu_thumbnail_fit", c_int32, [POINTER(WriteDesc), c_int32, POINTER(c_int32), POINTER(c_int32)]),
     ("avifgpu_thumbnail_from_sums", c_int32, [POINTER(WriteDesc), c_int32, c_int32, c_void_p, POINTER(_PLANES4), POINTER(_STRIDES4)]),
     ("avifgpu_probe_thumbnail", c_int32, [POINTER(WriteDesc), c_int32, c_int32, c_int32, POINTER(_PLANES4), POINTER(_STRIDES4), c_void_p, c_void_p]),
+    ("avifgpu_orientation_compose", c_int32, [c_int32, c_int32]),
+    ("avifgpu_read_oriented_geometry", c_int32, [POINTER(ReadDesc), c_int32, POINTER(c_int32), POINTER(c_int32)]),
+    ("avifgpu_read_oriented_next_tile", c_int32, [POINTER(ReadDesc), c_int32, c_int32, c_int32]),
+    ("avifgpu_read_oriented_scratch_bytes", c_int64, [POINTER(ReadDesc), c_int32, c_int32]),
+    ("avifgpu_read_rows_oriented", c_int32, [POINTER(ReadDesc), c_int32, c_int32, c_int32, POINTER(_PLANES4), POINTER(_STRIDES4),
+                                             c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p]),
+    ("avifgpu_probe_orient", c_int32, [c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
 ]
 
 
@@ -244,7 +251,10 @@ ABI4_NEW = frozenset(("avifgpu_probe_pattern_read", "avifgpu_probe_pattern_rgb32
                       "avifgpu_icc_clut8_from_transforms", "avifgpu_write_rows_icc8_table", "avifgpu_probe_set_shape",        # (ABI 5, round 6)
                       "avifgpu_histogram_attach", "avifgpu_light_level_from_histogram", "avifgpu_probe_histogram",
                       "avifgpu_host_save_wants_light_level",    # (the code histogram)
-                      "avifgpu_thumbnail_attach", "avifgpu_thumbnail_fit", "avifgpu_thumbnail_from_sums", "avifgpu_probe_thumbnail"))   # (the thumbnail)
+                      "avifgpu_thumbnail_attach", "avifgpu_thumbnail_fit", "avifgpu_thumbnail_from_sums", "avifgpu_probe_thumbnail",   # (the thumbnail)
+                      "avifgpu_orientation_compose", "avifgpu_read_oriented_geometry", "avifgpu_read_oriented_next_tile",
+                      "avifgpu_read_oriented_scratch_bytes", "avifgpu_read_rows_oriented", "avifgpu_probe_orient",
+                      "avifgpu_host_read_heif_image_oriented"))    # (the oriented open)
 
 
 def bind(lib: ctypes.CDLL, table=ABI) -> ctypes.CDLL:
@@ -387,6 +397,17 @@ class AvifGpu:
         self._check(self.lib.avifgpu_read_rows(ctypes.byref(desc), row0, nrows,
                                                ctypes.byref(planes4(src_ptrs)), ctypes.byref(strides4(src_strides)),
                                                dst_ptr, dst_row_bytes, mem, stream or None))
+
+    def read_rows_oriented(self, desc: ReadDesc, orientation, orow0, onrows, src_ptrs, src_strides, dst_ptr, dst_row_bytes,
+                           scratch_ptr=None, scratch_bytes=0, mem=MEM_DEVICE, stream=0):
+        """Output rows [orow0, orow0 + onrows) of the oriented open (avifgpu_read_rows_oriented): src_ptrs are the WHOLE image's planes."""
+        self._check(self.lib.avifgpu_read_rows_oriented(ctypes.byref(desc), orientation, orow0, onrows,
+                                                        ctypes.byref(planes4(src_ptrs)), ctypes.byref(strides4(src_strides)),
+                                                        dst_ptr, dst_row_bytes, scratch_ptr or None, scratch_bytes, mem, stream or None))
+
+    def probe_orient(self, orientation, bytes_per_pixel, width, height, src, src_row_bytes, dst, dst_row_bytes, stream=None):
+        """Launch the orient kernel alone on device buffers (avifgpu_probe_orient)."""
+        self._check(self.lib.avifgpu_probe_orient(orientation, bytes_per_pixel, width, height, src, src_row_bytes, dst, dst_row_bytes, stream))
 
     def topology(self):
         """[{device, pci_bus_id, numa_node, cpulist, workers, workers_pinned}] of the bound devices (avifgpu_device_topology)."""
@@ -553,6 +574,35 @@ def thumbnail_from_sums(desc: WriteDesc, tw: int, th: int, sums, stride_pad: int
     if code != 0:
         raise AvifGpuError(code, lib.avifgpu_last_error().decode())
     return bufs
+
+
+def _oserr(code):
+    lib = load()
+    if code < 0:
+        raise AvifGpuError(code, lib.avifgpu_last_error().decode())
+    return code
+
+
+def orientation_compose(first: int, then: int) -> int:
+    """The EXIF code of "apply `first`, then `then`" (avifgpu_orientation_compose)."""
+    return _oserr(load().avifgpu_orientation_compose(first, then))
+
+
+def read_oriented_geometry(desc: ReadDesc, orientation: int):
+    """(width, height) of the oriented open (avifgpu_read_oriented_geometry)."""
+    w, h = c_int32(0), c_int32(0)
+    _oserr(load().avifgpu_read_oriented_geometry(ctypes.byref(desc), orientation, ctypes.byref(w), ctypes.byref(h)))
+    return w.value, h.value
+
+
+def read_oriented_next_tile(desc: ReadDesc, orientation: int, orow0: int, max_rows: int) -> int:
+    """Rows of the tile that starts at output row orow0 (avifgpu_read_oriented_next_tile)."""
+    return _oserr(load().avifgpu_read_oriented_next_tile(ctypes.byref(desc), orientation, orow0, max_rows))
+
+
+def read_oriented_scratch_bytes(desc: ReadDesc, orientation: int, onrows: int) -> int:
+    """Device scratch a MEM_DEVICE call of onrows output rows needs (avifgpu_read_oriented_scratch_bytes)."""
+    return _oserr(load().avifgpu_read_oriented_scratch_bytes(ctypes.byref(desc), orientation, onrows))
 
 
 def yuv_coefficients(has_nclx: int, matrix: int, primaries: int):

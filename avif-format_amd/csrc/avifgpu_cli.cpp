@@ -40,7 +40,7 @@ struct Args {
     int width = 0, height = 0, depth = 8, planes = 3, bits = 8, transfer = AVIFGPU_TRANSFER_CLIP, peak = 1000;
     int alpha = AVIFGPU_ALPHA_NONE, output = AVIFGPU_OUT_REFERENCE, chroma = AVIFGPU_CHROMA_444;
     int matrix = AVIFGPU_MATRIX_BT601, primaries = AVIFGPU_PRIMARIES_BT709, tc = 2, limited = 0, colorspace = AVIFGPU_COLORSPACE_YCBCR;
-    int lossless = 0, maxdata = 0, device = 0, hlg_ootf = 0, nclx = 0, keep_profile = 0, light_level = 0, thumb_bbox = 0;
+    int lossless = 0, maxdata = 0, device = 0, hlg_ootf = 0, nclx = 0, keep_profile = 0, light_level = 0, thumb_bbox = 0, orientation = 0;
     float gamma = 1.2f;
     double percentile = 1.0;
 };
@@ -55,7 +55,7 @@ struct Args {
         "                         [--light-level [--percentile P]] [--thumbnail BBOX THUMB.planes] IN.raw OUT.planes\n"
         "       avifgpu_cli read  --width W --height H --depth 8|16|32 --bits 8|10|12 --colorspace ycbcr|rgb|mono [--chroma 444|422|420]\n"
         "                         [--alpha none|straight|premultiplied] [--matrix N --primaries N --tc N [--limited]] [--peak NITS]\n"
-        "                         [--hlg-ootf --gamma G] [--maxdata BYTES] [--device N] IN.planes OUT.raw\n");
+        "                         [--hlg-ootf --gamma G] [--orientation 1..8] [--maxdata BYTES] [--device N] IN.planes OUT.raw\n");
     exit(2);
 }
 
@@ -95,6 +95,7 @@ Args parse(int argc, char** argv)
         else if (o == "--percentile") a.percentile = atof(val());
         else if (o == "--thumbnail") { a.thumb_bbox = atoi(val()); a.thumb_out = val(); if (a.thumb_bbox < 1) usage("--thumbnail needs a bounding box >= 1"); }
         else if (o == "--icc") a.icc = val();
+        else if (o == "--orientation") { a.orientation = atoi(val()); if (a.orientation < 1 || a.orientation > 8) usage("--orientation needs an EXIF code 1..8"); }
         else if (o == "--transfer") a.transfer = pick(val(), {{"clip", AVIFGPU_TRANSFER_CLIP}, {"pq", AVIFGPU_TRANSFER_PQ}, {"smpte428", AVIFGPU_TRANSFER_SMPTE428}}, "--transfer");
         else if (o == "--alpha") a.alpha = pick(val(), {{"none", AVIFGPU_ALPHA_NONE}, {"straight", AVIFGPU_ALPHA_STRAIGHT}, {"premultiplied", AVIFGPU_ALPHA_PREMULTIPLIED}}, "--alpha");
         else if (o == "--ycbcr") { a.output = AVIFGPU_OUT_YCBCR; a.chroma = pick(val(), {{"444", AVIFGPU_CHROMA_444}, {"422", AVIFGPU_CHROMA_422}, {"420", AVIFGPU_CHROMA_420}}, "--ycbcr"); }
@@ -276,16 +277,22 @@ int do_read(const Args& a)
     fclose(in);
     const int planes = (a.colorspace == AVIFGPU_COLORSPACE_MONOCHROME ? 1 : 3) + (img.has_alpha ? 1 : 0);
     setup_record(a, planes);
+    if (a.orientation >= 5) {                                       // a quarter turn: the document is H wide and W high (avifgpu_read_oriented_geometry)
+        g_host.fr.imageSize32 = {a.width, a.height};
+        g_host.fr.imageSize = {(int16_t)(a.width > 32767 ? 32767 : a.width), (int16_t)(a.height > 32767 ? 32767 : a.height)};
+    }
     g_host.file = fopen(a.out.c_str(), "wb");
     if (!g_host.file) { perror(a.out.c_str()); return 1; }
     g_host.saving = false;
     avifgpu_nclx nclx{a.primaries, a.tc, a.matrix, (uint8_t)!a.limited};
     avifgpu_LoadUIOptions lo{};
     lo.pq.nominalPeakBrightness = a.peak; lo.hlg.applyOOTF = (uint8_t)a.hlg_ootf; lo.hlg.displayGamma = a.gamma; lo.hlg.nominalPeakBrightness = a.peak;
-    const int rc = avifgpu_host_read_heif_image(&img, a.alpha, (a.nclx || a.depth == 32) ? &nclx : nullptr, &lo, &g_host.fr);
+    // --orientation: IN.planes is the STORED image, OUT.raw the oriented one (irot / imir applied on the GPU)
+    const int rc = a.orientation ? avifgpu_host_read_heif_image_oriented(&img, a.orientation, a.alpha, (a.nclx || a.depth == 32) ? &nclx : nullptr, &lo, &g_host.fr)
+                                 : avifgpu_host_read_heif_image(&img, a.alpha, (a.nclx || a.depth == 32) ? &nclx : nullptr, &lo, &g_host.fr);
     fclose(g_host.file);
     avifgpu_image_free(&img);
-    if (rc) return fail("avifgpu_host_read_heif_image", rc);
+    if (rc) return fail(a.orientation ? "avifgpu_host_read_heif_image_oriented" : "avifgpu_host_read_heif_image", rc);
     fprintf(stderr, "read: %dx%d %d-bit -> host depth %d, %d planes, %d tiles, maxValue %d\n", a.width, a.height, a.bits, a.depth,
             planes, g_host.tiles, g_host.fr.maxValue);
     return 0;

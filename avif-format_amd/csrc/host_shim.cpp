@@ -297,11 +297,12 @@ void CreateHeifImageInto(FormatRecordPtr formatRecord, AlphaState alphaState, co
 }
 
 // ---- read ------------------------------------------------------------------------------------------------
-void ReadHeifImageCommon(const avifgpu_image* image, AlphaState alphaState, const avifgpu_nclx* nclxProfile,
-                         const LoadUIOptions* loadOptions, FormatRecordPtr formatRecord)
+// SetupFormatRecord and the descriptor of an open: `stored` is the size of the planes, imageSize the document's (they differ for an
+// oriented open with a quarter turn)
+avifgpu_read_desc PrepareRead(const avifgpu_image* image, AlphaState alphaState, const avifgpu_nclx* nclxProfile, const LoadUIOptions* loadOptions,
+                              FormatRecordPtr formatRecord, const VPoint& imageSize, const VPoint& stored)
 {
     if (formatRecord->depth == 32 && nclxProfile == nullptr) throw std::runtime_error("The nclxProfile is null.");   // ReadHeifImage.cpp:870,956
-    const VPoint imageSize = GetImageSize(formatRecord);
     const bool hasAlpha = alphaState != AlphaState::None;
 
     // SetupFormatRecord, ReadHeifImage.cpp:31-50
@@ -315,7 +316,7 @@ void ReadHeifImageCommon(const avifgpu_image* image, AlphaState alphaState, cons
 
     avifgpu_read_desc d;
     std::memset(&d, 0, sizeof(d));
-    d.width = imageSize.h; d.height = imageSize.v;
+    d.width = stored.h; d.height = stored.v;
     d.colorspace = image->colorspace; d.chroma = image->chroma; d.bit_depth = image->bit_depth;
     d.depth = formatRecord->depth; d.alpha_state = (int)alphaState;
     d.has_nclx = nclxProfile != nullptr;
@@ -331,6 +332,14 @@ void ReadHeifImageCommon(const avifgpu_image* image, AlphaState alphaState, cons
     const int expectPlanes = (d.colorspace == AVIFGPU_COLORSPACE_MONOCHROME ? 1 : 3) + (hasAlpha ? 1 : 0);
     if (formatRecord->planes != expectPlanes) throw OSErrException(AVIFGPU_formatBadParameters);
     if (d.depth == 16) formatRecord->maxValue = avifgpu_read_max_value(&d);              // ReadHeifImage.cpp:206,499,747
+    return d;
+}
+
+void ReadHeifImageCommon(const avifgpu_image* image, AlphaState alphaState, const avifgpu_nclx* nclxProfile,
+                         const LoadUIOptions* loadOptions, FormatRecordPtr formatRecord)
+{
+    const VPoint imageSize = GetImageSize(formatRecord);
+    const avifgpu_read_desc d = PrepareRead(image, alphaState, nclxProfile, loadOptions, formatRecord, imageSize, imageSize);
 
     const bool even = d.colorspace == AVIFGPU_COLORSPACE_YCBCR && d.chroma == AVIFGPU_CHROMA_420;
     const int ys = even ? 1 : 0;
@@ -372,6 +381,47 @@ void ReadHeifImageCommon(const avifgpu_image* image, AlphaState alphaState, cons
     }
     formatRecord->data = nullptr;
     OSErrException::ThrowIfError((OSErr)avifgpu::wait_all());
+}
+
+// The oriented open (avifgpu_read_rows_oriented): the planes are the STORED image, the document is the oriented one.  Tiles are cut with
+// avifgpu_read_oriented_next_tile, converted one at a time into one pinned buffer (the library stages each through its own two slots) and
+// handed over top to bottom.
+void ReadHeifImageOriented(const avifgpu_image* image, int orientation, AlphaState alphaState, const avifgpu_nclx* nclxProfile,
+                           const LoadUIOptions* loadOptions, FormatRecordPtr formatRecord)
+{
+    const VPoint imageSize = GetImageSize(formatRecord);
+    if (orientation < 1 || orientation > 8) { avifgpu::set_error("orientation is not an EXIF code 1..8"); throw OSErrException(AVIFGPU_formatBadParameters); }
+    const bool turned = orientation >= 5;
+    VPoint stored;
+    stored.h = image->width; stored.v = image->height;
+    if (imageSize.h != (turned ? stored.v : stored.h) || imageSize.v != (turned ? stored.h : stored.v)) {
+        avifgpu::set_error("the document's size is not the oriented size of the image (avifgpu_read_oriented_geometry)");
+        throw OSErrException(AVIFGPU_formatBadParameters);
+    }
+    if (orientation == 1) { ReadHeifImageCommon(image, alphaState, nclxProfile, loadOptions, formatRecord); return; }
+    const avifgpu_read_desc d = PrepareRead(image, alphaState, nclxProfile, loadOptions, formatRecord, imageSize, stored);
+    if (avifgpu::context_count() == 0) { avifgpu::set_error("avifgpu_init has not succeeded: no HIP device bound (no CPU fallback)"); throw OSErrException(AVIFGPU_formatBadParameters); }
+
+    const int maxRows = rows_per_tile(formatRecord->maxData, formatRecord->rowBytes, imageSize.v, false);
+    void* const tile = avifgpu::tile_buffer(0, 0, (size_t)maxRows * (size_t)formatRecord->rowBytes);
+    if (!tile) throw std::bad_alloc();
+    const void* src[4]; int64_t stride[4];
+    for (int pl = 0; pl < 4; ++pl) { src[pl] = image->plane[pl]; stride[pl] = image->stride[pl]; }
+    auto bail = [&](OSErr e) { formatRecord->data = nullptr; throw OSErrException(e); };
+    const int32_t left = 0, right = imageSize.h;
+    for (int32_t top = 0; top < imageSize.v;) {
+        if (formatRecord->abortProc && formatRecord->abortProc()) bail(AVIFGPU_userCanceledErr);
+        const int32_t n = avifgpu_read_oriented_next_tile(&d, orientation, top, maxRows);
+        if (n <= 0) bail(n < 0 ? (OSErr)n : AVIFGPU_readErr);
+        const int err = avifgpu_read_rows_oriented(&d, orientation, top, n, src, stride, tile, formatRecord->rowBytes, nullptr, 0, AVIFGPU_MEM_HOST, nullptr);
+        if (err) bail((OSErr)err);
+        formatRecord->data = tile;
+        SetRect(formatRecord, top, left, top + n, right);
+        const OSErr herr = formatRecord->advanceState();
+        if (herr != AVIFGPU_noErr) bail(herr);
+        top += n;
+    }
+    formatRecord->data = nullptr;
 }
 
 // Exception -> OSErr exactly as the Do* drivers do it (Write.cpp:345-364, Read.cpp:659-678).
@@ -511,6 +561,16 @@ avifgpu_OSErr avifgpu_host_read_heif_image(const avifgpu_image* image, int32_t a
     return guarded([&] {
         avifgpu::HostCallGuard serial;
         ReadHeifImageCommon(image, (AlphaState)alphaState, nclxProfile, loadOptions, formatRecord);
+    }, AVIFGPU_readErr);
+}
+
+avifgpu_OSErr avifgpu_host_read_heif_image_oriented(const avifgpu_image* image, int32_t orientation, int32_t alphaState, const avifgpu_nclx* nclxProfile,
+                                                    const avifgpu_LoadUIOptions* loadOptions, avifgpu_FormatRecord* formatRecord)
+{
+    if (!image || !formatRecord || !formatRecord->advanceState) return AVIFGPU_formatBadParameters;
+    return guarded([&] {
+        avifgpu::HostCallGuard serial;
+        ReadHeifImageOriented(image, orientation, (AlphaState)alphaState, nclxProfile, loadOptions, formatRecord);
     }, AVIFGPU_readErr);
 }
 

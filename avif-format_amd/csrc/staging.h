@@ -70,6 +70,9 @@ void thumbnail_rows_of_tile(const avifgpu_write_desc* d, const WriteGeom& g, int
 hipError_t launch_thumbnail(const avifgpu_write_desc* d, const WriteGeom& g, int row0, int nrows, const uint8_t* const planes[4],
                             const int64_t stride[4], int tw, int th, unsigned long long* sums, hipStream_t st, int twin = 0);   // twin: avifgpu_probe_thumbnail
 
+// ---- orient_kernels.hip: irot / imir orientation of an open (avifgpu_read_rows_oriented) ------------------------------
+void release_orient_staging();                       // the host path's two staging slots (avifgpu_shutdown); nothing to do if never used
+
 // ---- write_kernels.hip / read_kernels.hip ---------------------------------------------------------------------------
 hipError_t launch_write(const WriteParams& p, int depth, int planes, bool dst16, int output, int xs, int ys,
                         int variant, hipStream_t st, char* label);

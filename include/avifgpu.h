@@ -687,6 +687,62 @@ int32_t avifgpu_write_rows_icc_pipeline32(const avifgpu_write_desc* desc, const 
                                           void* const dst[4], const int64_t dst_stride[4],
                                           int32_t mem_kind, void* stream);
 
+/* ---- oriented open: the file's irot / imir properties applied on the GPU ------------------------------------------------------------
+ * The reference decodes with heif_decode_image(handle, &img, colorSpace, chroma, nullptr) (Read.cpp:99): with no decoding options libheif
+ * applies the item's `irot` and `imir` to the decoded planes before the plug-in sees them, and the plug-in resets the EXIF orientation to
+ * top-left because of it (ReadMetadata.cpp:105-107).  An adapter that sets ignore_transformations gets the STORED planes and asks for
+ * the orientation here instead.  An orientation is one of the eight EXIF codes.  With I the H x W x C array of host
+ * samples avifgpu_read_rows produces for `desc` and its planes, the oriented open yields EXACTLY (numpy on I; no tolerance, floats too):
+ *     1  I                          W x H        5  I.transpose(1, 0, 2)                  H x W
+ *     2  I[:, ::-1]                 W x H        6  np.rot90(I, -1)  (clockwise)           H x W
+ *     3  I[::-1, ::-1]              W x H        7  I[::-1, ::-1].transpose(1, 0, 2)       H x W
+ *     4  I[::-1, :]                 W x H        8  np.rot90(I, 1)   (anticlockwise)       H x W
+ * irot with angle a (anticlockwise quarter turns) is np.rot90(I, a): codes 1, 8, 3, 6; imir is code 2 or code 4.  The definition is in
+ * the PIXEL domain: chroma is upsampled as the reference does it (nearest: x >> xs, y >> ys), then pixels are moved.  Where a subsampled
+ * dimension is even that equals moving the planes first; where it is odd the two differ by one chroma sample's phase, and a quarter turn
+ * of 4:2:2 has no plane-domain form at all (what libheif 1.14.0 does there is not verified).  The clean aperture (clap)
+ * is not applied.
+ *
+ * Output rows [orow0, orow0 + onrows) correspond to a source REGION -- a row range for codes 1-4, a column band for codes 5-8 -- that the
+ * existing read kernels decode as a sub-image into scratch; a kernel of a code object of its own then moves whole pixels from scratch to
+ * dst.  Where the cut direction is subsampled the region must start on an even source index (a region of ONE row / column may start
+ * anywhere: it is its own chroma sample); with a flipped direction of odd size that makes the first tile odd, so callers cut with
+ * avifgpu_read_oriented_next_tile. */
+
+/* "apply `first`, then `then`" as one code.  Host only; closed over 1..8; formatBadParameters (negative) outside. */
+int32_t avifgpu_orientation_compose(int32_t first, int32_t then);
+
+/* Size of the oriented image: (W, H) for codes 1-4, (H, W) for codes 5-8. */
+int32_t avifgpu_read_oriented_geometry(const avifgpu_read_desc* desc, int32_t orientation, int32_t* out_w, int32_t* out_h);
+
+/* The largest onrows <= max_rows (max_rows >= 1) that output row orow0 may be followed by: all of max_rows, or the rest of the image,
+ * where the cut direction is not subsampled; otherwise such that this tile's source region and the next one's both start on an even
+ * index (or are single).  Always > 0 inside the image, so tiles cut with it partition the image for every max_rows; a negative OSErr
+ * for bad arguments.  Host only. */
+int32_t avifgpu_read_oriented_next_tile(const avifgpu_read_desc* desc, int32_t orientation, int32_t orow0, int32_t max_rows);
+
+/* Device scratch a MEM_DEVICE call for `onrows` output rows needs: the decoded sub-image (rows padded to 256 bytes); 0 for code 1. */
+int64_t avifgpu_read_oriented_scratch_bytes(const avifgpu_read_desc* desc, int32_t orientation, int32_t onrows);
+
+/* Open output rows [orow0, orow0 + onrows) of the oriented image.  src[i] / src_stride[i] are the planes of the WHOLE stored image (row 0,
+ * the plane order of avifgpu_read_rows); dst is the first byte of output row orow0; bytes of a dst row beyond out_w * bytes per pixel are
+ * not touched.  AVIFGPU_MEM_DEVICE: `scratch` is the caller's device memory (avifgpu_read_oriented_scratch_bytes), the decode and the
+ * orient kernel are enqueued on `stream` and the call does not synchronise.  AVIFGPU_MEM_HOST: scratch is NULL (ignored); the library
+ * stages tiles of the range through two slots of its own on the FIRST bound context (planes up, decode, orient, rows down -- column bands
+ * go up and down as strided copies); the bytes are the same for every number of bound contexts, pinned or pageable memory.  Code 1 is
+ * avifgpu_read_rows on the range.  formatBadParameters before anything is launched for a code outside 1..8, an illegal cut, too little
+ * scratch, too small dst_row_bytes. */
+int32_t avifgpu_read_rows_oriented(const avifgpu_read_desc* desc, int32_t orientation, int32_t orow0, int32_t onrows,
+                                   const void* const src[4], const int64_t src_stride[4],
+                                   void* dst, int64_t dst_row_bytes,
+                                   void* scratch, int64_t scratch_bytes,
+                                   int32_t mem_kind, void* stream);
+
+/* Measuring aid (tools/bench_orient.py): the orient kernel ALONE on device pointers -- a width x height image of bytes_per_pixel-byte
+ * pixels (1, 2, 3, 4, 6, 8, 12, 16) at src, moved by code 2..8 to dst (height x width for codes 5-8), on `stream`. */
+int32_t avifgpu_probe_orient(int32_t orientation, int32_t bytes_per_pixel, int32_t width, int32_t height,
+                             const void* src, int64_t src_row_bytes, void* dst, int64_t dst_row_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -186,6 +186,15 @@ avifgpu_OSErr avifgpu_host_read_heif_image(const avifgpu_image* image, int32_t a
                                            const avifgpu_nclx* nclxProfile, const avifgpu_LoadUIOptions* loadOptions,
                                            avifgpu_FormatRecord* formatRecord);
 
+/* The same with the item's orientation (an EXIF code 1..8: irot / imir composed with avifgpu_orientation_compose) applied on the GPU
+ * (avifgpu_read_rows_oriented, include/avifgpu.h): `image` holds the STORED planes -- decoded with ignore_transformations -- and
+ * formatRecord's image size must be the oriented size (avifgpu_read_oriented_geometry), else AVIFGPU_formatBadParameters.  The oriented
+ * image is delivered top to bottom through advanceState() in tiles sized from maxData and cut with avifgpu_read_oriented_next_tile;
+ * abortProc is asked before every tile.  Orientation 1 is avifgpu_host_read_heif_image. */
+avifgpu_OSErr avifgpu_host_read_heif_image_oriented(const avifgpu_image* image, int32_t orientation, int32_t alphaState,
+                                                    const avifgpu_nclx* nclxProfile, const avifgpu_LoadUIOptions* loadOptions,
+                                                    avifgpu_FormatRecord* formatRecord);
+
 /* ==== Decisions of the reference-named adapters, as C-ABI helpers =====================================================
  * Everything integration/WriteHeifImage_gpu.cpp / ReadHeifImage_gpu.cpp (the twelve reference-named functions, compiled only
  * against the real Photoshop SDK + libheif headers) has to DECIDE lives here, where it is compiled and tested without those
