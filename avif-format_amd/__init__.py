@@ -37,6 +37,7 @@ DOWNSAMPLE_AVERAGE, DOWNSAMPLE_NEAREST = 0, 1
 CHROMA_ZERO_LIBHEIF, CHROMA_ZERO_DECODER = 0, 1
 PQ_AUTO, PQ_COMPACT, PQ_CLOSE = 0, 1, 2
 MEM_HOST, MEM_DEVICE = 0, 1
+UPSAMPLE_NEAREST, UPSAMPLE_BILINEAR_CENTER, UPSAMPLE_BILINEAR_LEFT = 0, 1, 2
 
 noErr, userCanceledErr, readErr, writErr, memFullErr = 0, -128, -19, -20, -108
 formatBadParameters, formatCannotRead = -30500, -30501
@@ -239,6 +240,11 @@ ABI = [
     ("avifgpu_read_rows_oriented", c_int32, [POINTER(ReadDesc), c_int32, c_int32, c_int32, POINTER(_PLANES4), POINTER(_STRIDES4),
                                              c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p]),
     ("avifgpu_probe_orient", c_int32, [c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    ("avifgpu_read_upsampled_scratch_bytes", c_int64, [POINTER(ReadDesc), c_int32, c_int32, c_int32]),
+    ("avifgpu_read_rows_upsampled", c_int32, [POINTER(ReadDesc), c_int32, c_int32, c_int32, c_int32, POINTER(_PLANES4), POINTER(_STRIDES4),
+                                              c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p]),
+    ("avifgpu_probe_upsample", c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                         POINTER(c_void_p * 2), POINTER(c_int64 * 2), POINTER(c_void_p * 2), c_int64, c_int32, c_void_p]),
 ]
 
 
@@ -254,7 +260,9 @@ ABI4_NEW = frozenset(("avifgpu_probe_pattern_read", "avifgpu_probe_pattern_rgb32
                       "avifgpu_thumbnail_attach", "avifgpu_thumbnail_fit", "avifgpu_thumbnail_from_sums", "avifgpu_probe_thumbnail",   # (the thumbnail)
                       "avifgpu_orientation_compose", "avifgpu_read_oriented_geometry", "avifgpu_read_oriented_next_tile",
                       "avifgpu_read_oriented_scratch_bytes", "avifgpu_read_rows_oriented", "avifgpu_probe_orient",
-                      "avifgpu_host_read_heif_image_oriented"))    # (the oriented open)
+                      "avifgpu_host_read_heif_image_oriented",    # (the oriented open)
+                      "avifgpu_read_upsampled_scratch_bytes", "avifgpu_read_rows_upsampled", "avifgpu_probe_upsample",
+                      "avifgpu_host_read_heif_image_upsampled"))   # (the upsampled open)
 
 
 def bind(lib: ctypes.CDLL, table=ABI) -> ctypes.CDLL:
@@ -404,6 +412,20 @@ class AvifGpu:
         self._check(self.lib.avifgpu_read_rows_oriented(ctypes.byref(desc), orientation, orow0, onrows,
                                                         ctypes.byref(planes4(src_ptrs)), ctypes.byref(strides4(src_strides)),
                                                         dst_ptr, dst_row_bytes, scratch_ptr or None, scratch_bytes, mem, stream or None))
+
+    def read_rows_upsampled(self, desc: ReadDesc, upsampling, orientation, orow0, onrows, src_ptrs, src_strides, dst_ptr, dst_row_bytes,
+                            scratch_ptr=None, scratch_bytes=0, mem=MEM_DEVICE, stream=0):
+        """Output rows [orow0, orow0 + onrows) of the (oriented) open with interpolated chroma (avifgpu_read_rows_upsampled): src_ptrs are
+        the WHOLE image's planes."""
+        self._check(self.lib.avifgpu_read_rows_upsampled(ctypes.byref(desc), upsampling, orientation, orow0, onrows,
+                                                         ctypes.byref(planes4(src_ptrs)), ctypes.byref(strides4(src_strides)),
+                                                         dst_ptr, dst_row_bytes, scratch_ptr or None, scratch_bytes, mem, stream or None))
+
+    def probe_upsample(self, bytes_per_sample, chroma, upsampling, width, height, x0, y0, w, h, src, src_strides, dst, dst_row_bytes, stream=None, twin=0):
+        """Launch the chroma upsample kernel alone on device buffers (avifgpu_probe_upsample): src / dst are (Cb, Cr) pointer pairs; twin 1 / 2: its store-only / math-free twin."""
+        self._check(self.lib.avifgpu_probe_upsample(bytes_per_sample, chroma, upsampling, width, height, x0, y0, w, h,
+                                                    ctypes.byref((c_void_p * 2)(*src)), ctypes.byref((c_int64 * 2)(*src_strides)),
+                                                    ctypes.byref((c_void_p * 2)(*dst)), dst_row_bytes, twin, stream))
 
     def probe_orient(self, orientation, bytes_per_pixel, width, height, src, src_row_bytes, dst, dst_row_bytes, stream=None):
         """Launch the orient kernel alone on device buffers (avifgpu_probe_orient)."""
@@ -598,6 +620,11 @@ def read_oriented_geometry(desc: ReadDesc, orientation: int):
 def read_oriented_next_tile(desc: ReadDesc, orientation: int, orow0: int, max_rows: int) -> int:
     """Rows of the tile that starts at output row orow0 (avifgpu_read_oriented_next_tile)."""
     return _oserr(load().avifgpu_read_oriented_next_tile(ctypes.byref(desc), orientation, orow0, max_rows))
+
+
+def read_upsampled_scratch_bytes(desc: ReadDesc, upsampling: int, orientation: int, onrows: int) -> int:
+    """Device scratch a MEM_DEVICE call of onrows output rows of the upsampled open needs (avifgpu_read_upsampled_scratch_bytes)."""
+    return _oserr(load().avifgpu_read_upsampled_scratch_bytes(ctypes.byref(desc), upsampling, orientation, onrows))
 
 
 def read_oriented_scratch_bytes(desc: ReadDesc, orientation: int, onrows: int) -> int:

@@ -386,8 +386,9 @@ void ReadHeifImageCommon(const avifgpu_image* image, AlphaState alphaState, cons
 // The oriented open (avifgpu_read_rows_oriented): the planes are the STORED image, the document is the oriented one.  Tiles are cut with
 // avifgpu_read_oriented_next_tile, converted one at a time into one pinned buffer (the library stages each through its own two slots) and
 // handed over top to bottom.
+// With `upsampling` (avifgpu_read_rows_upsampled) the chroma of a 4:2:x image is interpolated; AVIFGPU_UPSAMPLE_NEAREST is the oriented open.
 void ReadHeifImageOriented(const avifgpu_image* image, int orientation, AlphaState alphaState, const avifgpu_nclx* nclxProfile,
-                           const LoadUIOptions* loadOptions, FormatRecordPtr formatRecord)
+                           const LoadUIOptions* loadOptions, FormatRecordPtr formatRecord, int upsampling = AVIFGPU_UPSAMPLE_NEAREST)
 {
     const VPoint imageSize = GetImageSize(formatRecord);
     if (orientation < 1 || orientation > 8) { avifgpu::set_error("orientation is not an EXIF code 1..8"); throw OSErrException(AVIFGPU_formatBadParameters); }
@@ -398,7 +399,10 @@ void ReadHeifImageOriented(const avifgpu_image* image, int orientation, AlphaSta
         avifgpu::set_error("the document's size is not the oriented size of the image (avifgpu_read_oriented_geometry)");
         throw OSErrException(AVIFGPU_formatBadParameters);
     }
-    if (orientation == 1) { ReadHeifImageCommon(image, alphaState, nclxProfile, loadOptions, formatRecord); return; }
+    if (upsampling < AVIFGPU_UPSAMPLE_NEAREST || upsampling > AVIFGPU_UPSAMPLE_BILINEAR_LEFT) { avifgpu::set_error("chroma upsampling is not an AVIFGPU_UPSAMPLE_* value"); throw OSErrException(AVIFGPU_formatBadParameters); }
+    const bool interpolated = upsampling != AVIFGPU_UPSAMPLE_NEAREST && image->colorspace == AVIFGPU_COLORSPACE_YCBCR &&
+                              (image->chroma == AVIFGPU_CHROMA_420 || image->chroma == AVIFGPU_CHROMA_422);
+    if (orientation == 1 && !interpolated) { ReadHeifImageCommon(image, alphaState, nclxProfile, loadOptions, formatRecord); return; }
     const avifgpu_read_desc d = PrepareRead(image, alphaState, nclxProfile, loadOptions, formatRecord, imageSize, stored);
     if (avifgpu::context_count() == 0) { avifgpu::set_error("avifgpu_init has not succeeded: no HIP device bound (no CPU fallback)"); throw OSErrException(AVIFGPU_formatBadParameters); }
 
@@ -413,7 +417,8 @@ void ReadHeifImageOriented(const avifgpu_image* image, int orientation, AlphaSta
         if (formatRecord->abortProc && formatRecord->abortProc()) bail(AVIFGPU_userCanceledErr);
         const int32_t n = avifgpu_read_oriented_next_tile(&d, orientation, top, maxRows);
         if (n <= 0) bail(n < 0 ? (OSErr)n : AVIFGPU_readErr);
-        const int err = avifgpu_read_rows_oriented(&d, orientation, top, n, src, stride, tile, formatRecord->rowBytes, nullptr, 0, AVIFGPU_MEM_HOST, nullptr);
+        const int err = interpolated ? avifgpu_read_rows_upsampled(&d, upsampling, orientation, top, n, src, stride, tile, formatRecord->rowBytes, nullptr, 0, AVIFGPU_MEM_HOST, nullptr)
+                                     : avifgpu_read_rows_oriented(&d, orientation, top, n, src, stride, tile, formatRecord->rowBytes, nullptr, 0, AVIFGPU_MEM_HOST, nullptr);
         if (err) bail((OSErr)err);
         formatRecord->data = tile;
         SetRect(formatRecord, top, left, top + n, right);
@@ -571,6 +576,16 @@ avifgpu_OSErr avifgpu_host_read_heif_image_oriented(const avifgpu_image* image, 
     return guarded([&] {
         avifgpu::HostCallGuard serial;
         ReadHeifImageOriented(image, orientation, (AlphaState)alphaState, nclxProfile, loadOptions, formatRecord);
+    }, AVIFGPU_readErr);
+}
+
+avifgpu_OSErr avifgpu_host_read_heif_image_upsampled(const avifgpu_image* image, int32_t orientation, int32_t upsampling, int32_t alphaState,
+                                                     const avifgpu_nclx* nclxProfile, const avifgpu_LoadUIOptions* loadOptions, avifgpu_FormatRecord* formatRecord)
+{
+    if (!image || !formatRecord || !formatRecord->advanceState) return AVIFGPU_formatBadParameters;
+    return guarded([&] {
+        avifgpu::HostCallGuard serial;
+        ReadHeifImageOriented(image, orientation, (AlphaState)alphaState, nclxProfile, loadOptions, formatRecord, upsampling);
     }, AVIFGPU_readErr);
 }
 

@@ -73,6 +73,9 @@ hipError_t launch_thumbnail(const avifgpu_write_desc* d, const WriteGeom& g, int
 // ---- orient_kernels.hip: irot / imir orientation of an open (avifgpu_read_rows_oriented) ------------------------------
 void release_orient_staging();                       // the host path's two staging slots (avifgpu_shutdown); nothing to do if never used
 
+// ---- upsample_kernels.hip: bilinear chroma upsampling of a 4:2:x open (avifgpu_read_rows_upsampled) ----------------------------------
+void release_upsample_staging();                     // the host path's two staging slots (avifgpu_shutdown); nothing to do if never used
+
 // ---- write_kernels.hip / read_kernels.hip ---------------------------------------------------------------------------
 hipError_t launch_write(const WriteParams& p, int depth, int planes, bool dst16, int output, int xs, int ys,
                         int variant, hipStream_t st, char* label);

@@ -91,6 +91,8 @@ HOST_ABI = [
                                                POINTER(FormatRecord)]),
     ("avifgpu_host_read_heif_image_oriented", c_int16, [POINTER(Image), c_int32, c_int32, POINTER(Nclx), POINTER(LoadUIOptions),
                                                         POINTER(FormatRecord)]),
+    ("avifgpu_host_read_heif_image_upsampled", c_int16, [POINTER(Image), c_int32, c_int32, c_int32, POINTER(Nclx), POINTER(LoadUIOptions),
+                                                         POINTER(FormatRecord)]),
     # decisions of the reference-named adapters (csrc/host_decisions.cpp)
     ("avifgpu_host_image_bit_depth", c_int32, [c_int32]),
     ("avifgpu_host_chroma_subsampling", c_int32, [c_int32, c_int32]),

@@ -743,6 +743,63 @@ int32_t avifgpu_read_rows_oriented(const avifgpu_read_desc* desc, int32_t orient
 int32_t avifgpu_probe_orient(int32_t orientation, int32_t bytes_per_pixel, int32_t width, int32_t height,
                              const void* src, int64_t src_row_bytes, void* dst, int64_t dst_row_bytes, void* stream);
 
+/* ---- upsampled open: 4:2:0 / 4:2:2 chroma interpolated instead of replicated ------------------------------------------------------------
+ * Every other open replicates chroma (x >> xs, y >> ys), as the reference does (YuvDecode.cpp:302, ReadHeifImage.cpp:143); that stays the
+ * default.  This is the read-side counterpart of AVIFGPU_DOWNSAMPLE_AVERAGE: an extension for adapters that want what later decoders are
+ * believed to show (libheif >= 1.16 and libavif through libyuv are said to interpolate by default; the agreement of these taps with
+ * either is NOT verified).  The definition is integer and exact.  For a YCbCr image of W x H with xs = 1 (4:2:0: ys = 1, 4:2:2: ys = 0)
+ * each chroma plane C of cw = (W + 1) >> 1 by ch = (H + ys) >> ys samples is replaced by a plane U of W x H samples in the same
+ * container type.  Taps are (index, weight in quarters), indices clamped to [0, cw - 1] / [0, ch - 1] (edge replication):
+ *     horizontal, i = x >> 1   CENTER   even x: (i - 1, 1), (i, 3)     odd x: (i, 3), (i + 1, 1)
+ *                              LEFT     even x: (i, 4)                 odd x: (i, 2), (i + 1, 2)
+ *     vertical, j = y >> 1     4:2:0, both modes: the CENTER rule on y;    4:2:2: (y, 4)
+ *     U[y, x] = (sum_a sum_b wy_a wx_b C[jy_a, ix_b] + 8) >> 4            -- ONE rounding of the joint 16-weight sum
+ * on the raw container values as unsigned integers (a 10- / 12-bit sample above 2^bits - 1 is filtered as it is; the decode behind it
+ * applies its own rule).  CENTER is the midpoint siting (AV1 chroma sample position "unknown", JPEG style); LEFT is AV1's "vertical":
+ * co-sited with even luma columns, midway between rows.  "Colocated" is not offered.
+ *
+ * The upsampled open IS avifgpu_read_rows on the same descriptor with chroma = 4:4:4 and the planes (Y, U(Cb), U(Cr), A): every matrix,
+ * range, transfer, alpha state, host depth and out-of-range rule is that of the 4:4:4 open.  With an orientation it is orient(code, .) of
+ * that image, as avifgpu_read_rows_oriented defines it.  AVIFGPU_UPSAMPLE_NEAREST, a 4:4:4, a monochrome and a planar-RGB image yield the
+ * bytes of avifgpu_read_rows_oriented (code 1: avifgpu_read_rows), whatever the mode. */
+enum {
+    AVIFGPU_UPSAMPLE_NEAREST         = 0,
+    AVIFGPU_UPSAMPLE_BILINEAR_CENTER = 1,
+    AVIFGPU_UPSAMPLE_BILINEAR_LEFT   = 2
+};
+
+/* Device scratch a MEM_DEVICE call for `onrows` output rows needs.  With the source region of those rows sw x sh (W x onrows for codes
+ * 1-4, onrows x H for codes 5-8), s bytes per plane sample and b bytes per host pixel:
+ *     2 * align256(sw * s) * sh   (the two upsampled chroma rectangles)   +   codes 2-8: align256(sw * b) * sh   (the oriented open's)
+ * 0 where the call degenerates to an existing entry point (such a call hands `scratch` on to avifgpu_read_rows_oriented: size it with
+ * avifgpu_read_oriented_scratch_bytes).  A negative OSErr for an unknown enum or a bad descriptor.  Host only: needs no device. */
+int64_t avifgpu_read_upsampled_scratch_bytes(const avifgpu_read_desc* desc, int32_t upsampling, int32_t orientation, int32_t onrows);
+
+/* Open output rows [orow0, orow0 + onrows) of the (oriented) upsampled image.  Arguments as for avifgpu_read_rows_oriented: src[i] are the
+ * planes of the WHOLE stored image -- which is why this is an entry of its own: avifgpu_read_rows gets planes advanced to its first row and
+ * cannot see the chroma row above a tile -- and tiles are cut with avifgpu_read_oriented_next_tile (even source indices).  The bytes of a
+ * tile do not depend on the tiling.  AVIFGPU_MEM_DEVICE: the upsample kernel (a code object of its own), the existing 4:4:4 open on
+ * (Y, scratch Cb, scratch Cr, A) and for codes 2-8 the existing orient kernels are enqueued on `stream`; the call does not synchronise.
+ * AVIFGPU_MEM_HOST: scratch is ignored; tiles are staged through two slots of the library's own on the FIRST bound context; of the chroma
+ * planes only the region's samples plus a halo (one sample; 8 bytes of them on the left, for alignment) on each side that exists go up.  The bytes are the same for every number of bound
+ * contexts, pinned or pageable memory.  formatBadParameters before anything is launched for an unknown upsampling or orientation, an
+ * illegal cut, too little scratch, too small dst_row_bytes. */
+int32_t avifgpu_read_rows_upsampled(const avifgpu_read_desc* desc, int32_t upsampling, int32_t orientation, int32_t orow0, int32_t onrows,
+                                    const void* const src[4], const int64_t src_stride[4],
+                                    void* dst, int64_t dst_row_bytes,
+                                    void* scratch, int64_t scratch_bytes,
+                                    int32_t mem_kind, void* stream);
+
+/* Measuring aid (tools/bench_upsample.py): the upsample kernel ALONE on device pointers.  src[0..1] are the whole Cb / Cr planes of a
+ * width x height image of `chroma` (AVIFGPU_CHROMA_420 | 422) with bytes_per_sample 1 | 2; rectangle [x0, x0 + w) x [y0, y0 + h) of U(Cb)
+ * and U(Cr) goes to dst[0..1] (first byte = sample (y0, x0)), on `stream`.  upsampling: one of the two bilinear modes.  twin 0 = the kernel
+ * itself; 1 = its store-only twin (no source load, no cross-lane move), 2 = its math-free twin (the same loads and stores, no neighbour
+ * samples, no sums) -- CENTER only, for attribution: what they leave in dst is meaningless. */
+int32_t avifgpu_probe_upsample(int32_t bytes_per_sample, int32_t chroma, int32_t upsampling, int32_t width, int32_t height,
+                               int32_t x0, int32_t y0, int32_t w, int32_t h,
+                               const void* const src[2], const int64_t src_stride[2],
+                               void* const dst[2], int64_t dst_row_bytes, int32_t twin, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

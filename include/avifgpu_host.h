@@ -195,6 +195,14 @@ avifgpu_OSErr avifgpu_host_read_heif_image_oriented(const avifgpu_image* image, 
                                                     const avifgpu_nclx* nclxProfile, const avifgpu_LoadUIOptions* loadOptions,
                                                     avifgpu_FormatRecord* formatRecord);
 
+/* ... and with the chroma of a 4:2:0 / 4:2:2 image interpolated instead of replicated (`upsampling`: AVIFGPU_UPSAMPLE_*,
+ * avifgpu_read_rows_upsampled, include/avifgpu.h).  Everything else as above: the stored planes, the oriented size, tiles top to bottom
+ * sized from maxData and cut with avifgpu_read_oriented_next_tile, abortProc asked before every tile.  AVIFGPU_UPSAMPLE_NEAREST is
+ * avifgpu_host_read_heif_image_oriented; an unknown value is AVIFGPU_formatBadParameters before anything is delivered. */
+avifgpu_OSErr avifgpu_host_read_heif_image_upsampled(const avifgpu_image* image, int32_t orientation, int32_t upsampling, int32_t alphaState,
+                                                     const avifgpu_nclx* nclxProfile, const avifgpu_LoadUIOptions* loadOptions,
+                                                     avifgpu_FormatRecord* formatRecord);
+
 /* ==== Decisions of the reference-named adapters, as C-ABI helpers =====================================================
  * Everything integration/WriteHeifImage_gpu.cpp / ReadHeifImage_gpu.cpp (the twelve reference-named functions, compiled only
  * against the real Photoshop SDK + libheif headers) has to DECIDE lives here, where it is compiled and tested without those
