@@ -154,6 +154,14 @@ def icc_pipeline32_from_profile(profile_bytes: bytes, target=ICC_TARGET_REC2020_
     return rc, t
 
 
+class CropRect(ctypes.Structure):
+    """avifgpu_rect: a rectangle in STORED image coordinates."""
+    _fields_ = [("x0", c_int32), ("y0", c_int32), ("width", c_int32), ("height", c_int32)]
+
+    def astuple(self):
+        return (self.x0, self.y0, self.width, self.height)
+
+
 class ContentLightLevel(ctypes.Structure):
     """avifgpu_content_light_level: the clli fields and what they were rounded from."""
     _fields_ = [("max_cll", ctypes.c_uint16), ("max_fall", ctypes.c_uint16), ("max_code", c_int32), ("pixels", ctypes.c_uint64),
@@ -245,6 +253,14 @@ ABI = [
                                               c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p]),
     ("avifgpu_probe_upsample", c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                          POINTER(c_void_p * 2), POINTER(c_int64 * 2), POINTER(c_void_p * 2), c_int64, c_int32, c_void_p]),
+    ("avifgpu_clap_to_rect", c_int32, [c_int32, c_int32, POINTER(c_int32 * 8), POINTER(CropRect)]),
+    ("avifgpu_crop_compose", c_int32, [POINTER(CropRect), c_int32, POINTER(CropRect), POINTER(CropRect)]),
+    ("avifgpu_read_cropped_geometry", c_int32, [POINTER(ReadDesc), POINTER(CropRect), c_int32, POINTER(c_int32), POINTER(c_int32)]),
+    ("avifgpu_read_cropped_next_tile", c_int32, [POINTER(ReadDesc), POINTER(CropRect), c_int32, c_int32, c_int32, c_int32]),
+    ("avifgpu_read_cropped_scratch_bytes", c_int64, [POINTER(ReadDesc), POINTER(CropRect), c_int32, c_int32, c_int32]),
+    ("avifgpu_read_rows_cropped", c_int32, [POINTER(ReadDesc), POINTER(CropRect), c_int32, c_int32, c_int32, c_int32, POINTER(_PLANES4), POINTER(_STRIDES4),
+                                            c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p]),
+    ("avifgpu_probe_crop", c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p]),
 ]
 
 
@@ -262,7 +278,10 @@ ABI4_NEW = frozenset(("avifgpu_probe_pattern_read", "avifgpu_probe_pattern_rgb32
                       "avifgpu_read_oriented_scratch_bytes", "avifgpu_read_rows_oriented", "avifgpu_probe_orient",
                       "avifgpu_host_read_heif_image_oriented",    # (the oriented open)
                       "avifgpu_read_upsampled_scratch_bytes", "avifgpu_read_rows_upsampled", "avifgpu_probe_upsample",
-                      "avifgpu_host_read_heif_image_upsampled"))   # (the upsampled open)
+                      "avifgpu_host_read_heif_image_upsampled",   # (the upsampled open)
+                      "avifgpu_clap_to_rect", "avifgpu_crop_compose", "avifgpu_read_cropped_geometry", "avifgpu_read_cropped_next_tile",
+                      "avifgpu_read_cropped_scratch_bytes", "avifgpu_read_rows_cropped", "avifgpu_probe_crop",
+                      "avifgpu_host_read_heif_image_cropped"))   # (the cropped open)
 
 
 def bind(lib: ctypes.CDLL, table=ABI) -> ctypes.CDLL:
@@ -420,6 +439,18 @@ class AvifGpu:
         self._check(self.lib.avifgpu_read_rows_upsampled(ctypes.byref(desc), upsampling, orientation, orow0, onrows,
                                                          ctypes.byref(planes4(src_ptrs)), ctypes.byref(strides4(src_strides)),
                                                          dst_ptr, dst_row_bytes, scratch_ptr or None, scratch_bytes, mem, stream or None))
+
+    def read_rows_cropped(self, desc: ReadDesc, rect, upsampling, orientation, orow0, onrows, src_ptrs, src_strides, dst_ptr, dst_row_bytes,
+                          scratch_ptr=None, scratch_bytes=0, mem=MEM_DEVICE, stream=0):
+        """Output rows [orow0, orow0 + onrows) of the cropped (upsampled, oriented) open (avifgpu_read_rows_cropped): rect is (x0, y0, w, h) in
+        the stored image, src_ptrs are the WHOLE image's planes."""
+        self._check(self.lib.avifgpu_read_rows_cropped(ctypes.byref(desc), ctypes.byref(crop_rect(rect)), upsampling, orientation, orow0, onrows,
+                                                       ctypes.byref(planes4(src_ptrs)), ctypes.byref(strides4(src_strides)),
+                                                       dst_ptr, dst_row_bytes, scratch_ptr or None, scratch_bytes, mem, stream or None))
+
+    def probe_crop(self, src, src_row_bytes, dst, dst_row_bytes, row_payload_bytes, rows, stream=None):
+        """Launch the crop mover kernel alone on device buffers (avifgpu_probe_crop)."""
+        self._check(self.lib.avifgpu_probe_crop(src, src_row_bytes, dst, dst_row_bytes, row_payload_bytes, rows, stream))
 
     def probe_upsample(self, bytes_per_sample, chroma, upsampling, width, height, x0, y0, w, h, src, src_strides, dst, dst_row_bytes, stream=None, twin=0):
         """Launch the chroma upsample kernel alone on device buffers (avifgpu_probe_upsample): src / dst are (Cb, Cr) pointer pairs; twin 1 / 2: its store-only / math-free twin."""
@@ -625,6 +656,42 @@ def read_oriented_next_tile(desc: ReadDesc, orientation: int, orow0: int, max_ro
 def read_upsampled_scratch_bytes(desc: ReadDesc, upsampling: int, orientation: int, onrows: int) -> int:
     """Device scratch a MEM_DEVICE call of onrows output rows of the upsampled open needs (avifgpu_read_upsampled_scratch_bytes)."""
     return _oserr(load().avifgpu_read_upsampled_scratch_bytes(ctypes.byref(desc), upsampling, orientation, onrows))
+
+
+def crop_rect(rect) -> CropRect:
+    """A CropRect from (x0, y0, width, height) or a CropRect."""
+    return rect if isinstance(rect, CropRect) else CropRect(*rect)
+
+
+def clap_to_rect(width: int, height: int, clap) -> tuple:
+    """(x0, y0, w, h) of a clean aperture (widthN, D, heightN, D, horizOffN, D, vertOffN, D) in a width x height image (avifgpu_clap_to_rect)."""
+    out = CropRect()
+    _oserr(load().avifgpu_clap_to_rect(width, height, ctypes.byref((c_int32 * 8)(*clap)), ctypes.byref(out)))
+    return out.astuple()
+
+
+def crop_compose(current, code: int, crop_in_view) -> tuple:
+    """The stored rectangle of a crop given in the view orient(code, F[current]) (avifgpu_crop_compose)."""
+    out = CropRect()
+    _oserr(load().avifgpu_crop_compose(ctypes.byref(crop_rect(current)), code, ctypes.byref(crop_rect(crop_in_view)), ctypes.byref(out)))
+    return out.astuple()
+
+
+def read_cropped_geometry(desc: ReadDesc, rect, orientation: int):
+    """(width, height) of the cropped, oriented open (avifgpu_read_cropped_geometry)."""
+    w, h = c_int32(), c_int32()
+    _oserr(load().avifgpu_read_cropped_geometry(ctypes.byref(desc), ctypes.byref(crop_rect(rect)), orientation, ctypes.byref(w), ctypes.byref(h)))
+    return w.value, h.value
+
+
+def read_cropped_next_tile(desc: ReadDesc, rect, upsampling: int, orientation: int, orow0: int, max_rows: int) -> int:
+    """Rows of the tile that starts at output row orow0 (avifgpu_read_cropped_next_tile)."""
+    return _oserr(load().avifgpu_read_cropped_next_tile(ctypes.byref(desc), ctypes.byref(crop_rect(rect)), upsampling, orientation, orow0, max_rows))
+
+
+def read_cropped_scratch_bytes(desc: ReadDesc, rect, upsampling: int, orientation: int, onrows: int) -> int:
+    """Device scratch that is enough for any MEM_DEVICE call of onrows output rows of the cropped open (avifgpu_read_cropped_scratch_bytes)."""
+    return _oserr(load().avifgpu_read_cropped_scratch_bytes(ctypes.byref(desc), ctypes.byref(crop_rect(rect)), upsampling, orientation, onrows))
 
 
 def read_oriented_scratch_bytes(desc: ReadDesc, orientation: int, onrows: int) -> int:

@@ -888,6 +888,7 @@ void avifgpu_shutdown(void)
     release_device_caches();
     release_orient_staging();
     release_upsample_staging();
+    release_crop_staging();
 }
 
 int32_t avifgpu_get_yuv_coefficients(int32_t has_nclx, int32_t matrix_coefficients, int32_t color_primaries, float out[3])

@@ -41,6 +41,7 @@ struct Args {
     int alpha = AVIFGPU_ALPHA_NONE, output = AVIFGPU_OUT_REFERENCE, chroma = AVIFGPU_CHROMA_444;
     int matrix = AVIFGPU_MATRIX_BT601, primaries = AVIFGPU_PRIMARIES_BT709, tc = 2, limited = 0, colorspace = AVIFGPU_COLORSPACE_YCBCR;
     int lossless = 0, maxdata = 0, device = 0, hlg_ootf = 0, nclx = 0, keep_profile = 0, light_level = 0, thumb_bbox = 0, orientation = 0, upsampling = AVIFGPU_UPSAMPLE_NEAREST;
+    int crop = 0, crop_x0 = 0, crop_y0 = 0, crop_w = 0, crop_h = 0;
     float gamma = 1.2f;
     double percentile = 1.0;
 };
@@ -56,7 +57,7 @@ struct Args {
         "       avifgpu_cli read  --width W --height H --depth 8|16|32 --bits 8|10|12 --colorspace ycbcr|rgb|mono [--chroma 444|422|420]\n"
         "                         [--alpha none|straight|premultiplied] [--matrix N --primaries N --tc N [--limited]] [--peak NITS]\n"
         "                         [--hlg-ootf --gamma G] [--orientation 1..8] [--chroma-upsampling nearest|bilinear|bilinear-left]\n"
-        "                         [--maxdata BYTES] [--device N] IN.planes OUT.raw\n");
+        "                         [--crop X0,Y0,W,H] [--maxdata BYTES] [--device N] IN.planes OUT.raw\n");
     exit(2);
 }
 
@@ -97,6 +98,7 @@ Args parse(int argc, char** argv)
         else if (o == "--thumbnail") { a.thumb_bbox = atoi(val()); a.thumb_out = val(); if (a.thumb_bbox < 1) usage("--thumbnail needs a bounding box >= 1"); }
         else if (o == "--icc") a.icc = val();
         else if (o == "--orientation") { a.orientation = atoi(val()); if (a.orientation < 1 || a.orientation > 8) usage("--orientation needs an EXIF code 1..8"); }
+        else if (o == "--crop") { a.crop = 1; if (sscanf(val(), "%d,%d,%d,%d", &a.crop_x0, &a.crop_y0, &a.crop_w, &a.crop_h) != 4) usage("--crop needs X0,Y0,W,H"); }
         else if (o == "--chroma-upsampling") a.upsampling = pick(val(), {{"nearest", AVIFGPU_UPSAMPLE_NEAREST}, {"bilinear", AVIFGPU_UPSAMPLE_BILINEAR_CENTER}, {"bilinear-left", AVIFGPU_UPSAMPLE_BILINEAR_LEFT}}, "--chroma-upsampling");
         else if (o == "--transfer") a.transfer = pick(val(), {{"clip", AVIFGPU_TRANSFER_CLIP}, {"pq", AVIFGPU_TRANSFER_PQ}, {"smpte428", AVIFGPU_TRANSFER_SMPTE428}}, "--transfer");
         else if (o == "--alpha") a.alpha = pick(val(), {{"none", AVIFGPU_ALPHA_NONE}, {"straight", AVIFGPU_ALPHA_STRAIGHT}, {"premultiplied", AVIFGPU_ALPHA_PREMULTIPLIED}}, "--alpha");
@@ -279,9 +281,16 @@ int do_read(const Args& a)
     fclose(in);
     const int planes = (a.colorspace == AVIFGPU_COLORSPACE_MONOCHROME ? 1 : 3) + (img.has_alpha ? 1 : 0);
     setup_record(a, planes);
+    // --crop: a rectangle of the STORED image (the clean aperture); OUT.raw is orient(code, crop), composes with the two options below
+    const avifgpu_rect rect{a.crop_x0, a.crop_y0, a.crop_w, a.crop_h};
+    const int vw = a.crop ? a.crop_w : a.width, vh = a.crop ? a.crop_h : a.height;
+    if (a.crop) {
+        g_host.fr.imageSize32 = {vh, vw};
+        g_host.fr.imageSize = {(int16_t)(vh > 32767 ? 32767 : vh), (int16_t)(vw > 32767 ? 32767 : vw)};
+    }
     if (a.orientation >= 5) {                                       // a quarter turn: the document is H wide and W high (avifgpu_read_oriented_geometry)
-        g_host.fr.imageSize32 = {a.width, a.height};
-        g_host.fr.imageSize = {(int16_t)(a.width > 32767 ? 32767 : a.width), (int16_t)(a.height > 32767 ? 32767 : a.height)};
+        g_host.fr.imageSize32 = {vw, vh};
+        g_host.fr.imageSize = {(int16_t)(vw > 32767 ? 32767 : vw), (int16_t)(vh > 32767 ? 32767 : vh)};
     }
     g_host.file = fopen(a.out.c_str(), "wb");
     if (!g_host.file) { perror(a.out.c_str()); return 1; }
@@ -291,13 +300,14 @@ int do_read(const Args& a)
     lo.pq.nominalPeakBrightness = a.peak; lo.hlg.applyOOTF = (uint8_t)a.hlg_ootf; lo.hlg.displayGamma = a.gamma; lo.hlg.nominalPeakBrightness = a.peak;
     // --orientation: IN.planes is the STORED image, OUT.raw the oriented one (irot / imir applied on the GPU)
     // --chroma-upsampling: the chroma of a 4:2:x image is interpolated on the GPU (composes with --orientation)
-    const int rc = a.upsampling != AVIFGPU_UPSAMPLE_NEAREST
+    const int rc = a.crop ? avifgpu_host_read_heif_image_cropped(&img, &rect, a.orientation ? a.orientation : 1, a.upsampling, a.alpha, (a.nclx || a.depth == 32) ? &nclx : nullptr, &lo, &g_host.fr)
+                 : a.upsampling != AVIFGPU_UPSAMPLE_NEAREST
                        ? avifgpu_host_read_heif_image_upsampled(&img, a.orientation ? a.orientation : 1, a.upsampling, a.alpha, (a.nclx || a.depth == 32) ? &nclx : nullptr, &lo, &g_host.fr)
                  : a.orientation ? avifgpu_host_read_heif_image_oriented(&img, a.orientation, a.alpha, (a.nclx || a.depth == 32) ? &nclx : nullptr, &lo, &g_host.fr)
                                  : avifgpu_host_read_heif_image(&img, a.alpha, (a.nclx || a.depth == 32) ? &nclx : nullptr, &lo, &g_host.fr);
     fclose(g_host.file);
     avifgpu_image_free(&img);
-    if (rc) return fail(a.upsampling != AVIFGPU_UPSAMPLE_NEAREST ? "avifgpu_host_read_heif_image_upsampled" : a.orientation ? "avifgpu_host_read_heif_image_oriented" : "avifgpu_host_read_heif_image", rc);
+    if (rc) return fail(a.crop ? "avifgpu_host_read_heif_image_cropped" : a.upsampling != AVIFGPU_UPSAMPLE_NEAREST ? "avifgpu_host_read_heif_image_upsampled" : a.orientation ? "avifgpu_host_read_heif_image_oriented" : "avifgpu_host_read_heif_image", rc);
     fprintf(stderr, "read: %dx%d %d-bit -> host depth %d, %d planes, %d tiles, maxValue %d\n", a.width, a.height, a.bits, a.depth,
             planes, g_host.tiles, g_host.fr.maxValue);
     return 0;

@@ -429,6 +429,53 @@ void ReadHeifImageOriented(const avifgpu_image* image, int orientation, AlphaSta
     formatRecord->data = nullptr;
 }
 
+// The cropped open (avifgpu_read_rows_cropped): the planes are the STORED image, the document is orient(code, F[rect]).  As above, with the
+// tiles cut by avifgpu_read_cropped_next_tile.
+void ReadHeifImageCropped(const avifgpu_image* image, const avifgpu_rect& rect, int orientation, int upsampling, AlphaState alphaState,
+                          const avifgpu_nclx* nclxProfile, const LoadUIOptions* loadOptions, FormatRecordPtr formatRecord)
+{
+    const VPoint imageSize = GetImageSize(formatRecord);
+    if (orientation < 1 || orientation > 8) { avifgpu::set_error("orientation is not an EXIF code 1..8"); throw OSErrException(AVIFGPU_formatBadParameters); }
+    if (upsampling < AVIFGPU_UPSAMPLE_NEAREST || upsampling > AVIFGPU_UPSAMPLE_BILINEAR_LEFT) { avifgpu::set_error("chroma upsampling is not an AVIFGPU_UPSAMPLE_* value"); throw OSErrException(AVIFGPU_formatBadParameters); }
+    if (rect.x0 < 0 || rect.y0 < 0 || rect.width < 1 || rect.height < 1 || (int64_t)rect.x0 + rect.width > image->width || (int64_t)rect.y0 + rect.height > image->height) {
+        avifgpu::set_error("the rectangle is not inside the stored image"); throw OSErrException(AVIFGPU_formatBadParameters);
+    }
+    if (rect.x0 == 0 && rect.y0 == 0 && rect.width == image->width && rect.height == image->height) {
+        ReadHeifImageOriented(image, orientation, alphaState, nclxProfile, loadOptions, formatRecord, upsampling);
+        return;
+    }
+    const bool turned = orientation >= 5;
+    if (imageSize.h != (turned ? rect.height : rect.width) || imageSize.v != (turned ? rect.width : rect.height)) {
+        avifgpu::set_error("the document's size is not the cropped, oriented size of the image (avifgpu_read_cropped_geometry)");
+        throw OSErrException(AVIFGPU_formatBadParameters);
+    }
+    VPoint stored;
+    stored.h = image->width; stored.v = image->height;
+    const avifgpu_read_desc d = PrepareRead(image, alphaState, nclxProfile, loadOptions, formatRecord, imageSize, stored);
+    if (avifgpu::context_count() == 0) { avifgpu::set_error("avifgpu_init has not succeeded: no HIP device bound (no CPU fallback)"); throw OSErrException(AVIFGPU_formatBadParameters); }
+
+    const int maxRows = rows_per_tile(formatRecord->maxData, formatRecord->rowBytes, imageSize.v, false);
+    void* const tile = avifgpu::tile_buffer(0, 0, (size_t)maxRows * (size_t)formatRecord->rowBytes);
+    if (!tile) throw std::bad_alloc();
+    const void* src[4]; int64_t stride[4];
+    for (int pl = 0; pl < 4; ++pl) { src[pl] = image->plane[pl]; stride[pl] = image->stride[pl]; }
+    auto bail = [&](OSErr e) { formatRecord->data = nullptr; throw OSErrException(e); };
+    const int32_t left = 0, right = imageSize.h;
+    for (int32_t top = 0; top < imageSize.v;) {
+        if (formatRecord->abortProc && formatRecord->abortProc()) bail(AVIFGPU_userCanceledErr);
+        const int32_t n = avifgpu_read_cropped_next_tile(&d, &rect, upsampling, orientation, top, maxRows);
+        if (n <= 0) bail(n < 0 ? (OSErr)n : AVIFGPU_readErr);
+        const int err = avifgpu_read_rows_cropped(&d, &rect, upsampling, orientation, top, n, src, stride, tile, formatRecord->rowBytes, nullptr, 0, AVIFGPU_MEM_HOST, nullptr);
+        if (err) bail((OSErr)err);
+        formatRecord->data = tile;
+        SetRect(formatRecord, top, left, top + n, right);
+        const OSErr herr = formatRecord->advanceState();
+        if (herr != AVIFGPU_noErr) bail(herr);
+        top += n;
+    }
+    formatRecord->data = nullptr;
+}
+
 // Exception -> OSErr exactly as the Do* drivers do it (Write.cpp:345-364, Read.cpp:659-678).
 template <typename F> OSErr guarded(F&& f, OSErr fallback)
 {
@@ -586,6 +633,16 @@ avifgpu_OSErr avifgpu_host_read_heif_image_upsampled(const avifgpu_image* image,
     return guarded([&] {
         avifgpu::HostCallGuard serial;
         ReadHeifImageOriented(image, orientation, (AlphaState)alphaState, nclxProfile, loadOptions, formatRecord, upsampling);
+    }, AVIFGPU_readErr);
+}
+
+avifgpu_OSErr avifgpu_host_read_heif_image_cropped(const avifgpu_image* image, const avifgpu_rect* rect, int32_t orientation, int32_t upsampling, int32_t alphaState,
+                                                   const avifgpu_nclx* nclxProfile, const avifgpu_LoadUIOptions* loadOptions, avifgpu_FormatRecord* formatRecord)
+{
+    if (!image || !rect || !formatRecord || !formatRecord->advanceState) return AVIFGPU_formatBadParameters;
+    return guarded([&] {
+        avifgpu::HostCallGuard serial;
+        ReadHeifImageCropped(image, *rect, orientation, upsampling, (AlphaState)alphaState, nclxProfile, loadOptions, formatRecord);
     }, AVIFGPU_readErr);
 }
 

@@ -76,6 +76,9 @@ void release_orient_staging();                       // the host path's two stag
 // ---- upsample_kernels.hip: bilinear chroma upsampling of a 4:2:x open (avifgpu_read_rows_upsampled) ----------------------------------
 void release_upsample_staging();                     // the host path's two staging slots (avifgpu_shutdown); nothing to do if never used
 
+// ---- crop_kernels.hip: the clean aperture of an open (avifgpu_read_rows_cropped) ------------------------------------------------------
+void release_crop_staging();                         // the host path's two staging slots (avifgpu_shutdown); nothing to do if never used
+
 // ---- write_kernels.hip / read_kernels.hip ---------------------------------------------------------------------------
 hipError_t launch_write(const WriteParams& p, int depth, int planes, bool dst16, int output, int xs, int ys,
                         int variant, hipStream_t st, char* label);

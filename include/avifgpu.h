@@ -701,7 +701,7 @@ int32_t avifgpu_write_rows_icc_pipeline32(const avifgpu_write_desc* desc, const 
  * the PIXEL domain: chroma is upsampled as the reference does it (nearest: x >> xs, y >> ys), then pixels are moved.  Where a subsampled
  * dimension is even that equals moving the planes first; where it is odd the two differ by one chroma sample's phase, and a quarter turn
  * of 4:2:2 has no plane-domain form at all (what libheif 1.14.0 does there is not verified).  The clean aperture (clap)
- * is not applied.
+ * is applied by the cropped open below (avifgpu_read_rows_cropped), not by this entry.
  *
  * Output rows [orow0, orow0 + onrows) correspond to a source REGION -- a row range for codes 1-4, a column band for codes 5-8 -- that the
  * existing read kernels decode as a sub-image into scratch; a kernel of a code object of its own then moves whole pixels from scratch to
@@ -799,6 +799,90 @@ int32_t avifgpu_probe_upsample(int32_t bytes_per_sample, int32_t chroma, int32_t
                                int32_t x0, int32_t y0, int32_t w, int32_t h,
                                const void* const src[2], const int64_t src_stride[2],
                                void* const dst[2], int64_t dst_row_bytes, int32_t twin, void* stream);
+
+/* ---- cropped open: the file's clean aperture (clap) applied on the GPU ------------------------------------------------------------------
+ * libheif applies three transformative properties inside heif_decode_image: clap, irot and imir.  An adapter that decodes with
+ * ignore_transformations (which the oriented open needs) gets the STORED planes uncropped; this is the crop.  avifgpu_rect is a rectangle
+ * in STORED image coordinates: 0 <= x0, 1 <= width, x0 + width <= desc.width, and likewise in y.  With F the H x W x C array of host samples
+ * the un-oriented open of the whole image yields -- avifgpu_read_rows for AVIFGPU_UPSAMPLE_NEAREST, avifgpu_read_rows_upsampled(..., code
+ * 1, ...) for the two bilinear modes -- the cropped open of (rect, upsampling, code) is EXACTLY (no tolerance, floats too)
+ *     orient(code, F[y0 : y0 + height, x0 : x0 + width])
+ * with orient the table above avifgpu_read_rows_oriented: width x height for codes 1-4, height x width for codes 5-8.  The definition is in
+ * the PIXEL domain, like the oriented open's: an odd x0 / y0 of a 4:2:0 / 4:2:2 image keeps each pixel the chroma sample it has in the whole
+ * image ((x0 + x) >> 1), which advanced plane pointers cannot express, and the bilinear taps of a pixel at the rectangle's edge reach
+ * the chroma sample outside it and clamp at the PLANE's edge.  libheif's own crop works on the planes: it is believed to coincide for even
+ * x0 / y0 and may differ by one chroma sample's phase for odd ones; that is NOT verified (with the oriented open's two
+ * unverified corners). */
+typedef struct avifgpu_rect { int32_t x0, y0, width, height; } avifgpu_rect;
+
+/* The rectangle of a clean aperture in a width x height image.  Host only, exact rational arithmetic (128-bit integers).  clap holds
+ * cleanApertureWidthN, D, cleanApertureHeightN, D, horizOffN, D, vertOffN, D.  The rule is ISO 14496-12's: pcX = horizOff + (width - 1) / 2,
+ * left = pcX - (cleanApertureWidth - 1) / 2, right = pcX + (cleanApertureWidth - 1) / 2, top / bottom the same way; each edge is rounded half
+ * up, floor(v + 1/2); then left, top are clamped to >= 0 and right, bottom to <= size - 1; rect = (left, top, right - left + 1, bottom - top
+ * + 1).  formatBadParameters for a denominator <= 0, an aperture width or height <= 0 or an empty result (the aperture lies outside the
+ * image); 128 bits hold every intermediate of 32-bit operands, so no operand is rejected for its size.  libheif 1.14.0 is believed to compute the same for every aperture whose edges are >= 0;
+ * that is NOT verified.  Its rounding of a negative edge truncates toward zero, which after the clamp matters only for an aperture that lies
+ * wholly outside the image. */
+int32_t avifgpu_clap_to_rect(int32_t width, int32_t height, const int32_t clap[8], avifgpu_rect* out);
+
+/* Fold a crop into a view.  The current view is orient(code, F[current]); crop_in_view is a rectangle in THAT view's coordinates; out is the
+ * stored rectangle with orient(code, F[out]) == view[crop_in_view].  Host only.  An adapter folds the file's properties in their listed
+ * order, starting from (whole image, code 1): a clap goes through avifgpu_clap_to_rect on the VIEW's size and then through this helper, an
+ * irot / imir through avifgpu_orientation_compose.  formatBadParameters for a code outside 1..8, an empty or negative
+ * rectangle, a crop outside the view. */
+int32_t avifgpu_crop_compose(const avifgpu_rect* current, int32_t code, const avifgpu_rect* crop_in_view, avifgpu_rect* out);
+
+/* Size of the cropped, oriented image: (rect.width, rect.height) for codes 1-4, (rect.height, rect.width) for codes 5-8. */
+int32_t avifgpu_read_cropped_geometry(const avifgpu_read_desc* desc, const avifgpu_rect* rect, int32_t orientation, int32_t* out_w, int32_t* out_h);
+
+/* Every cut is legal for the cropped entry; a cut on an odd ABSOLUTE source index of a subsampled direction costs a nearest open one more
+ * decoded row / column and a pass of the mover.  Returns the largest onrows <= max_rows (max_rows >= 1) that avoids it where it can:
+ * where the cut direction runs forwards, such that the NEXT tile's source region starts on an even absolute index; where it runs backwards
+ * (the code flips it), such that THIS tile's does -- the last tile's region starts where the rectangle starts, whatever that is.  All of
+ * max_rows, or the rest of the image, where it does not matter (a bilinear mode, an image or a cut direction that is not subsampled).
+ * Always > 0 inside the image, so tiles cut with it partition the image for every max_rows; a negative OSErr for bad arguments.  Host only. */
+int32_t avifgpu_read_cropped_next_tile(const avifgpu_read_desc* desc, const avifgpu_rect* rect, int32_t upsampling, int32_t orientation,
+                                       int32_t orow0, int32_t max_rows);
+
+/* Device scratch that is enough for ANY MEM_DEVICE call of `onrows` output rows.  With the source region of those rows sw x sh (rect.width
+ * x onrows for codes 1-4, onrows x rect.height for codes 5-8), s bytes per plane sample and b bytes per host pixel:
+ *     a bilinear mode on a 4:2:0 / 4:2:2 image:   2 * align256(sw * s) * sh   +   codes 2-8: align256(sw * b) * sh     (the upsampled open's)
+ *     otherwise:                                   align256((sw + px) * b) * (sh + py);    0 for code 1 with px = py = 0
+ * px = 1 where the image is subsampled horizontally, sw > 1 and the region may start on an odd column (codes 5-8: always; codes 1-4: x0 is
+ * odd), py likewise for rows (codes 1-4: always; codes 5-8: y0 is odd).  A call needs only what ITS region needs (px, py from where it
+ * starts; none for a call that degenerates to an existing entry point beyond what that entry needs).  A negative OSErr for an unknown enum,
+ * a bad descriptor or rectangle.  Host only: needs no device. */
+int64_t avifgpu_read_cropped_scratch_bytes(const avifgpu_read_desc* desc, const avifgpu_rect* rect, int32_t upsampling, int32_t orientation,
+                                           int32_t onrows);
+
+/* Open output rows [orow0, orow0 + onrows) of the cropped (upsampled, oriented) image.  src[i] / src_stride[i] are the planes of the WHOLE
+ * stored image; everything else as for avifgpu_read_rows_upsampled; bytes of a dst row beyond the output row's pixels are not touched; the
+ * bytes of a tile do not depend on the tiling.  How a call is served:
+ *   - rect is the whole image (and the cut is one avifgpu_read_rows_upsampled takes): that entry, byte for byte;
+ *   - code 1 and no phase problem -- the image is not subsampled YCbCr, or the mode is bilinear, or every subsampled direction of the region
+ *     starts even or is a single row / column: the existing kernels write straight into dst from advanced pointers (a bilinear mode gives
+ *     chroma_upsample the rectangle); for a nearest call avifgpu_last_kernel_name() is what avifgpu_read_rows reports for an image of the
+ *     region's size;
+ *   - code 1, nearest, an odd start in a subsampled direction: the existing kernels decode the COVERING rectangle (the start rounded down
+ *     to even) into scratch and crop_rows -- a 2-D byte mover, a code object of its own -- moves the rows to dst from one pixel and / or
+ *     one row in;
+ *   - codes 2-8: decoded into scratch likewise, and the existing orient kernels run from the offset pixel.
+ * AVIFGPU_MEM_HOST: scratch is ignored.  A code-1 call with nothing to move whose advanced plane pointers stay on the 16-byte grid is
+ * avifgpu_read_rows on the sub-image (every bound context); anything else is staged in tiles through two slots of the library's own on the FIRST bound context: of every plane only the region's part
+ * goes up, as a strided copy, plus the covering row / column or the bilinear halo where needed.  The bytes are the same for every number of
+ * bound contexts, pinned or pageable memory.  formatBadParameters before anything is launched for a bad rectangle, upsampling, code or row
+ * range, too little scratch, too small dst_row_bytes. */
+int32_t avifgpu_read_rows_cropped(const avifgpu_read_desc* desc, const avifgpu_rect* rect, int32_t upsampling, int32_t orientation,
+                                  int32_t orow0, int32_t onrows,
+                                  const void* const src[4], const int64_t src_stride[4],
+                                  void* dst, int64_t dst_row_bytes,
+                                  void* scratch, int64_t scratch_bytes,
+                                  int32_t mem_kind, void* stream);
+
+/* Measuring and testing aid (tools/bench_crop.py): the mover kernel ALONE on device pointers -- `rows` rows of row_payload_bytes bytes from
+ * src (any address) to dst (any address, any stride), on `stream`; bytes of a dst row beyond the payload are not touched. */
+int32_t avifgpu_probe_crop(const void* src, int64_t src_row_bytes, void* dst, int64_t dst_row_bytes, int64_t row_payload_bytes, int32_t rows,
+                           void* stream);
 
 #ifdef __cplusplus
 }

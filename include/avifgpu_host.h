@@ -203,6 +203,15 @@ avifgpu_OSErr avifgpu_host_read_heif_image_upsampled(const avifgpu_image* image,
                                                      const avifgpu_nclx* nclxProfile, const avifgpu_LoadUIOptions* loadOptions,
                                                      avifgpu_FormatRecord* formatRecord);
 
+/* ... and with the item's clean aperture applied (`rect`: a rectangle of the STORED image, from avifgpu_clap_to_rect / avifgpu_crop_compose;
+ * avifgpu_read_rows_cropped, include/avifgpu.h).  formatRecord's image size must be the cropped, oriented size
+ * (avifgpu_read_cropped_geometry), else AVIFGPU_formatBadParameters.  Tiles go top to bottom, are sized from maxData and cut with
+ * avifgpu_read_cropped_next_tile; abortProc is asked before every tile.  A rect that is the whole image is
+ * avifgpu_host_read_heif_image_upsampled. */
+avifgpu_OSErr avifgpu_host_read_heif_image_cropped(const avifgpu_image* image, const avifgpu_rect* rect, int32_t orientation, int32_t upsampling,
+                                                   int32_t alphaState, const avifgpu_nclx* nclxProfile, const avifgpu_LoadUIOptions* loadOptions,
+                                                   avifgpu_FormatRecord* formatRecord);
+
 /* ==== Decisions of the reference-named adapters, as C-ABI helpers =====================================================
  * Everything integration/WriteHeifImage_gpu.cpp / ReadHeifImage_gpu.cpp (the twelve reference-named functions, compiled only
  * against the real Photoshop SDK + libheif headers) has to DECIDE lives here, where it is compiled and tested without those
