@@ -168,6 +168,17 @@ class ContentLightLevel(ctypes.Structure):
                 ("max_cll_nits", ctypes.c_double), ("max_fall_nits", ctypes.c_double)]
 
 
+class SaveSummary(ctypes.Structure):
+    """avifgpu_save_summary: what the summary counters of a save say (avifgpu_summary_read)."""
+    _fields_ = [("channels", c_int32), ("min_code", c_int32 * 4), ("max_code", c_int32 * 4), ("spread", c_int32),
+                ("alpha_opaque", c_int32), ("alpha_clear", c_int32), ("neutral", c_int32), ("advice", c_int32)]
+
+
+SUMMARY_COUNTERS = 16
+ADVICE_DROP_ALPHA = 1
+ADVICE_MONOCHROME = 2
+
+
 class DeviceInfo(ctypes.Structure):
     _fields_ = [("device", c_int32), ("numa_node", c_int32), ("workers", c_int32), ("workers_pinned", c_int32),
                 ("pci_bus_id", ctypes.c_char * 32), ("cpulist", ctypes.c_char * 256)]
@@ -241,6 +252,10 @@ ABI = [
     ("avifgpu_thumbnail_fit", c_int32, [POINTER(WriteDesc), c_int32, POINTER(c_int32), POINTER(c_int32)]),
     ("avifgpu_thumbnail_from_sums", c_int32, [POINTER(WriteDesc), c_int32, c_int32, c_void_p, POINTER(_PLANES4), POINTER(_STRIDES4)]),
     ("avifgpu_probe_thumbnail", c_int32, [POINTER(WriteDesc), c_int32, c_int32, c_int32, POINTER(_PLANES4), POINTER(_STRIDES4), c_void_p, c_void_p]),
+    ("avifgpu_summary_attach", c_int32, [c_void_p, c_int32]),
+    ("avifgpu_summary_read", c_int32, [POINTER(WriteDesc), c_void_p, POINTER(SaveSummary)]),
+    ("avifgpu_summary_merge", c_int32, [c_void_p, c_void_p]),
+    ("avifgpu_probe_summary", c_int32, [POINTER(WriteDesc), c_int32, POINTER(_PLANES4), POINTER(_STRIDES4), c_void_p, c_void_p]),
     ("avifgpu_orientation_compose", c_int32, [c_int32, c_int32]),
     ("avifgpu_read_oriented_geometry", c_int32, [POINTER(ReadDesc), c_int32, POINTER(c_int32), POINTER(c_int32)]),
     ("avifgpu_read_oriented_next_tile", c_int32, [POINTER(ReadDesc), c_int32, c_int32, c_int32]),
@@ -274,6 +289,7 @@ ABI4_NEW = frozenset(("avifgpu_probe_pattern_read", "avifgpu_probe_pattern_rgb32
                       "avifgpu_histogram_attach", "avifgpu_light_level_from_histogram", "avifgpu_probe_histogram",
                       "avifgpu_host_save_wants_light_level",    # (the code histogram)
                       "avifgpu_thumbnail_attach", "avifgpu_thumbnail_fit", "avifgpu_thumbnail_from_sums", "avifgpu_probe_thumbnail",   # (the thumbnail)
+                      "avifgpu_summary_attach", "avifgpu_summary_read", "avifgpu_summary_merge", "avifgpu_probe_summary",   # (the summary of a save)
                       "avifgpu_orientation_compose", "avifgpu_read_oriented_geometry", "avifgpu_read_oriented_next_tile",
                       "avifgpu_read_oriented_scratch_bytes", "avifgpu_read_rows_oriented", "avifgpu_probe_orient",
                       "avifgpu_host_read_heif_image_oriented",    # (the oriented open)
@@ -627,6 +643,60 @@ def thumbnail_from_sums(desc: WriteDesc, tw: int, th: int, sums, stride_pad: int
     if code != 0:
         raise AvifGpuError(code, lib.avifgpu_last_error().decode())
     return bufs
+
+
+def _summary_address(counters, what):
+    b = counters
+    if hasattr(b, "data_ptr"):
+        n, ptr, ok = b.numel(), b.data_ptr(), b.element_size() == 4 and b.is_contiguous()
+    elif hasattr(b, "ctypes"):
+        n, ptr, ok = b.size, b.ctypes.data, b.dtype.itemsize == 4 and b.flags["C_CONTIGUOUS"]
+    else:
+        return int(b)
+    if not ok or n < SUMMARY_COUNTERS:
+        raise ValueError("%s: counters must be %d contiguous 32-bit words" % (what, SUMMARY_COUNTERS))
+    return ptr
+
+
+class plane_summary:
+    """Arm the calling thread's summary counters for the `with` block, disarm them on the way out (avifgpu_summary_attach).
+
+    `counters` holds SUMMARY_COUNTERS 32-bit running maxima -- hi[4], lo_inv[4], spread, reserved -- and is never cleared by the library:
+    a numpy uint32 array (mem = MEM_HOST), a contiguous torch int32 tensor on the device the calls run on (mem = MEM_DEVICE), or a raw
+    address.  All-zero is the empty summary."""
+
+    def __init__(self, counters, mem=MEM_HOST):
+        self.counters, self.mem = counters, mem
+
+    def __enter__(self):
+        lib = load()
+        code = lib.avifgpu_summary_attach(_summary_address(self.counters, "plane_summary"), self.mem)
+        if code != 0:
+            raise AvifGpuError(code, lib.avifgpu_last_error().decode())
+        return self
+
+    def __exit__(self, *exc):
+        load().avifgpu_summary_attach(None, MEM_HOST)
+        return False
+
+
+def summary_read(desc: WriteDesc, counters) -> SaveSummary:
+    """What host counters (numpy uint32, SUMMARY_COUNTERS words) say about the save `desc` describes: avifgpu_summary_read."""
+    lib = load()
+    out = SaveSummary()
+    code = lib.avifgpu_summary_read(ctypes.byref(desc), _summary_address(counters, "summary_read"), ctypes.byref(out))
+    if code != 0:
+        raise AvifGpuError(code, lib.avifgpu_last_error().decode())
+    return out
+
+
+def summary_merge(into, other):
+    """into = max(into, other), element by element (host counters): avifgpu_summary_merge.  Returns `into`."""
+    lib = load()
+    code = lib.avifgpu_summary_merge(_summary_address(into, "summary_merge"), _summary_address(other, "summary_merge"))
+    if code != 0:
+        raise AvifGpuError(code, lib.avifgpu_last_error().decode())
+    return into
 
 
 def _oserr(code):

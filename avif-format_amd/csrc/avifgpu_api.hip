@@ -802,6 +802,8 @@ int write_rows_any(const avifgpu_write_desc* d, const IccArgs& icc, int32_t row0
     if ((err = histogram_for_call(d, mem_kind, &hist))) return err;            // before anything is launched
     ThumbArm thumb;
     if ((err = thumbnail_for_call(d, g, mem_kind, &thumb))) return err;        // likewise
+    uint32_t* summary = nullptr;
+    if ((err = summary_for_call(mem_kind, &summary))) return err;              // likewise
     if (nrows == 0) return 0;
     if (icc.c16 || icc.s32 || icc.c8t) icc_epoch_for_call(row0, nrows);       // the device copies of these tables are re-verified once per device and epoch
 
@@ -821,6 +823,10 @@ int write_rows_any(const avifgpu_write_desc* d, const IccArgs& icc, int32_t row0
         if (thumb.sums) {                               // the planes just written, summed behind it on the caller's stream into the caller's device sums
             const hipError_t et = launch_thumbnail(d, g, row0, nrows, p.dst, p.dst_stride, thumb.tw, thumb.th, reinterpret_cast<unsigned long long*>(thumb.sums), st);
             if (et != hipSuccess) return hip_fail(et, "thumbnail kernel launch", AVIFGPU_writErr);
+        }
+        if (summary) {                                  // the same planes, their extremes raised behind it in the caller's device counters
+            const hipError_t es = launch_summary(d, g, row0, nrows, p.dst, p.dst_stride, summary, st);
+            if (es != hipSuccess) return hip_fail(es, "summary kernel launch", AVIFGPU_writErr);
         }
         return 0;
     }

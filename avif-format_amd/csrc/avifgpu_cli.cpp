@@ -40,7 +40,7 @@ struct Args {
     int width = 0, height = 0, depth = 8, planes = 3, bits = 8, transfer = AVIFGPU_TRANSFER_CLIP, peak = 1000;
     int alpha = AVIFGPU_ALPHA_NONE, output = AVIFGPU_OUT_REFERENCE, chroma = AVIFGPU_CHROMA_444;
     int matrix = AVIFGPU_MATRIX_BT601, primaries = AVIFGPU_PRIMARIES_BT709, tc = 2, limited = 0, colorspace = AVIFGPU_COLORSPACE_YCBCR;
-    int lossless = 0, maxdata = 0, device = 0, hlg_ootf = 0, nclx = 0, keep_profile = 0, light_level = 0, thumb_bbox = 0, orientation = 0, upsampling = AVIFGPU_UPSAMPLE_NEAREST;
+    int lossless = 0, maxdata = 0, device = 0, hlg_ootf = 0, nclx = 0, keep_profile = 0, light_level = 0, thumb_bbox = 0, summary = 0, orientation = 0, upsampling = AVIFGPU_UPSAMPLE_NEAREST;
     int crop = 0, crop_x0 = 0, crop_y0 = 0, crop_w = 0, crop_h = 0;
     float gamma = 1.2f;
     double percentile = 1.0;
@@ -53,7 +53,7 @@ struct Args {
         "usage: avifgpu_cli write --width W --height H --depth 8|16|32 --planes 1..4 --bits 8|10|12 [--transfer clip|pq|smpte428]\n"
         "                         [--peak NITS] [--alpha none|straight|premultiplied] [--ycbcr 444|422|420] [--matrix N] [--primaries N]\n"
         "                         [--lossless] [--icc PROFILE [--keep-profile]] [--maxdata BYTES] [--device N]\n"
-        "                         [--light-level [--percentile P]] [--thumbnail BBOX THUMB.planes] IN.raw OUT.planes\n"
+        "                         [--light-level [--percentile P]] [--thumbnail BBOX THUMB.planes] [--summary] IN.raw OUT.planes\n"
         "       avifgpu_cli read  --width W --height H --depth 8|16|32 --bits 8|10|12 --colorspace ycbcr|rgb|mono [--chroma 444|422|420]\n"
         "                         [--alpha none|straight|premultiplied] [--matrix N --primaries N --tc N [--limited]] [--peak NITS]\n"
         "                         [--hlg-ootf --gamma G] [--orientation 1..8] [--chroma-upsampling nearest|bilinear|bilinear-left]\n"
@@ -96,6 +96,7 @@ Args parse(int argc, char** argv)
         else if (o == "--light-level") a.light_level = 1;
         else if (o == "--percentile") a.percentile = atof(val());
         else if (o == "--thumbnail") { a.thumb_bbox = atoi(val()); a.thumb_out = val(); if (a.thumb_bbox < 1) usage("--thumbnail needs a bounding box >= 1"); }
+        else if (o == "--summary") a.summary = 1;
         else if (o == "--icc") a.icc = val();
         else if (o == "--orientation") { a.orientation = atoi(val()); if (a.orientation < 1 || a.orientation > 8) usage("--orientation needs an EXIF code 1..8"); }
         else if (o == "--crop") { a.crop = 1; if (sscanf(val(), "%d,%d,%d,%d", &a.crop_x0, &a.crop_y0, &a.crop_w, &a.crop_h) != 4) usage("--crop needs X0,Y0,W,H"); }
@@ -197,7 +198,7 @@ int do_write(const Args& a)
     std::vector<uint64_t> tsums;
     avifgpu_write_desc td{};
     int32_t tw = 0, th = 0;
-    if (a.thumb_bbox) {
+    if (a.thumb_bbox || a.summary) {
         avifgpu_SaveUIOptions n = o;                                // the options the save will run with (Write.cpp:231-258)
         if (avifgpu_host_normalize_save_options(&g_host.fr, &n) != AVIFGPU_noErr) return fail("avifgpu_host_normalize_save_options", AVIFGPU_formatBadParameters);
         td.width = a.width; td.height = a.height; td.depth = a.depth; td.planes = a.planes;
@@ -206,10 +207,18 @@ int do_write(const Args& a)
         td.chroma = a.lossless ? AVIFGPU_CHROMA_444 : a.chroma;
         td.matrix_coefficients = a.lossless ? AVIFGPU_MATRIX_RGB_GBR : a.matrix; td.color_primaries = a.primaries;
         td.full_range = 1; td.chroma_downsampling = AVIFGPU_DOWNSAMPLE_AVERAGE; td.chroma_zero_point = AVIFGPU_CHROMA_ZERO_LIBHEIF;
+    }
+    if (a.thumb_bbox) {
         int trc = avifgpu_thumbnail_fit(&td, a.thumb_bbox, &tw, &th);
         if (trc) return fail("avifgpu_thumbnail_fit", trc);
         tsums.assign((size_t)tw * th * a.planes, 0);
         if ((trc = avifgpu_thumbnail_attach(tsums.data(), tw, th, AVIFGPU_MEM_HOST))) return fail("avifgpu_thumbnail_attach", trc);
+    }
+    // --summary: the range of every written channel, its counters armed around the shim's call on this thread (all tiles folded in)
+    uint32_t counters[AVIFGPU_SUMMARY_COUNTERS] = {};
+    if (a.summary) {
+        const int src = avifgpu_summary_attach(counters, AVIFGPU_MEM_HOST);
+        if (src) return fail("avifgpu_summary_attach", src);
     }
     avifgpu_image img{};
     const int rc = avifgpu_host_create_heif_image(&g_host.fr, a.alpha, &o, a.output, a.lossless ? AVIFGPU_MATRIX_RGB_GBR : a.matrix,
@@ -217,7 +226,16 @@ int do_write(const Args& a)
     fclose(g_host.file);
     if (a.light_level) (void)avifgpu_histogram_attach(nullptr, 0, AVIFGPU_MEM_HOST);
     if (a.thumb_bbox) (void)avifgpu_thumbnail_attach(nullptr, 0, 0, AVIFGPU_MEM_HOST);
+    if (a.summary) (void)avifgpu_summary_attach(nullptr, AVIFGPU_MEM_HOST);
     if (rc) return fail("avifgpu_host_create_heif_image", rc);
+    if (a.summary) {
+        avifgpu_save_summary sm{};
+        const int src = avifgpu_summary_read(&td, counters, &sm);
+        if (src) { avifgpu_image_free(&img); return fail("avifgpu_summary_read", src); }
+        printf("summary");
+        for (int c = 0; c < sm.channels; ++c) printf(" min%d %d max%d %d", c, (int)sm.min_code[c], c, (int)sm.max_code[c]);
+        printf(" spread %d alpha_opaque %d neutral %d advice %d\n", (int)sm.spread, (int)sm.alpha_opaque, (int)sm.neutral, (int)sm.advice);
+    }
     if (a.thumb_bbox) {
         // the thumbnail planes in the raw form of the main planes: tight rows, plane after plane
         const int ssz = td.bit_depth > 8 ? 2 : 1;

@@ -137,6 +137,23 @@ struct ThumbParams {
     int32_t twin;                // 1: avifgpu_probe_thumbnail's atomics-free twin (loads and register adds only; sums are not produced)
 };
 
+// The summary of a save's written planes (plane_summary, summary_kernels.hip): running maxima of the output codes a tile's conversion
+// kernel just wrote, raised in 32-bit counters in device memory with vector atomics (atomicMax)
+struct SummaryPlane {
+    const uint8_t* base[3];      // the plane at the tile's first row (chroma: row0 >> ys); [1], [2]: the B and R planes when G,B,R planes are read together
+    int64_t stride[3];           // bytes
+    int32_t pw, prows;           // the plane's width in pixels and the tile's plane rows
+    int32_t c0;                  // channel of the plane's first (interleaved or joint) channel in the counters (R,G,B[,A] | Y[,A] | Y,Cb,Cr[,A])
+    int32_t aligned;             // every base and stride is a multiple of 16: rows are read as 16-byte loads
+};
+struct SummaryParams {
+    SummaryPlane pl[4];          // grid.z picks one
+    uint32_t* counters;          // [AVIFGPU_SUMMARY_COUNTERS]: hi[4], lo_inv[4], spread, reserved
+    int32_t nslots;              // entries of pl[] in use
+    int32_t band_rows;           // consecutive plane rows per workgroup (launch_summary)
+    int32_t twin;                // 1: avifgpu_probe_summary's atomics-free twin (loads and register work only; counters are not produced)
+};
+
 struct ReadParams {
     const uint8_t* src[4];       // Y,Cb,Cr,A / R,G,B,A / Y,-,-,A at row row0 (chroma: row0 >> ys)
     int64_t        src_stride[4];

@@ -63,6 +63,7 @@ struct Job {
     IccArgs icc;
     bool hist = false;                                     // write, depth 32: the calling thread had a code histogram armed (enqueue side decides, the worker counts)
     int thumb_tw = 0, thumb_th = 0;                        // write: the calling thread had a thumbnail of this size armed (0: none)
+    bool summary = false;                                  // write: the calling thread had a summary armed (avifgpu_summary_attach)
     // filled by start(): what finish() still has to copy out of the pinned bounce buffer
     struct Bounce { uint8_t* dst; int64_t dst_stride; size_t off, pitch, bytes; int rows; } bounce[4];
     int nbounce = 0;
@@ -111,6 +112,11 @@ struct Ctx {
     unsigned long long* d_thumb = nullptr;
     size_t d_thumb_cap = 0;                                // counters
     int thumb_tw = 0, thumb_th = 0, thumb_c = 0, thumb_lo = 0, thumb_hi = 0;
+    // summary counters of the tiles this context converted for an armed caller (avifgpu_summary_attach): AVIFGPU_SUMMARY_COUNTERS running
+    // maxima on the device, allocated and zeroed by the worker on first use, freed when it exits; wait_all() max-merges them into the
+    // caller's counters and zeroes them
+    uint32_t* d_summary = nullptr;
+    std::atomic<bool> summary_dirty{false};
 };
 constexpr int kHistBins = 4096;
 
@@ -553,6 +559,20 @@ int start_write(Ctx& c, Job& j)
         e = launch_thumbnail(d, g, j.row0, j.nrows, p.dst, p.dst_stride, j.thumb_tw, j.thumb_th, c.d_thumb, st);
         if (e != hipSuccess) { (void)hipStreamSynchronize(st); return hip_fail(e, "thumbnail kernel launch", AVIFGPU_writErr); }
     }
+    if (j.summary) {
+        // the extremes of the planes that lie in d_out, likewise
+        if (!c.d_summary) {
+            void* sb = nullptr;
+            e = hipMalloc(&sb, AVIFGPU_SUMMARY_COUNTERS * sizeof(uint32_t));
+            if (e == hipSuccess) e = hipMemsetAsync(sb, 0, AVIFGPU_SUMMARY_COUNTERS * sizeof(uint32_t), st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);          // once per context: the other slots' streams raise them too
+            if (e != hipSuccess) { if (sb) (void)hipFree(sb); (void)hipStreamSynchronize(st); return hip_fail(e, "hipMalloc(summary counters)", AVIFGPU_memFullErr); }
+            c.d_summary = static_cast<uint32_t*>(sb);
+        }
+        c.summary_dirty.store(true, std::memory_order_release);
+        e = launch_summary(d, g, j.row0, j.nrows, p.dst, p.dst_stride, c.d_summary, st);
+        if (e != hipSuccess) { (void)hipStreamSynchronize(st); return hip_fail(e, "summary kernel launch", AVIFGPU_writErr); }
+    }
     if ((e = hipEventRecord(sl.done, st)) != hipSuccess) { (void)hipStreamSynchronize(st); return hip_fail(e, "event record", AVIFGPU_writErr); }
     return 0;
 }
@@ -757,6 +777,7 @@ void worker_main(Ctx* cp)
     }
     if (c.d_hist) { (void)hipFree(c.d_hist); c.d_hist = nullptr; }
     if (c.d_thumb) { (void)hipFree(c.d_thumb); c.d_thumb = nullptr; c.d_thumb_cap = 0; c.thumb_lo = c.thumb_hi = 0; }
+    if (c.d_summary) { (void)hipFree(c.d_summary); c.d_summary = nullptr; }
 }
 
 Ctx* ctx_at(int i)
@@ -1007,6 +1028,9 @@ int write_tile_enqueue(int ctx, int slot, const avifgpu_write_desc* d, int row0,
     ThumbArm thumb;                                        // likewise
     if ((err = thumbnail_for_call(d, g, AVIFGPU_MEM_HOST, &thumb))) return err;
     if (thumb.sums) { j.thumb_tw = thumb.tw; j.thumb_th = thumb.th; }
+    uint32_t* summary = nullptr;                           // likewise
+    if ((err = summary_for_call(AVIFGPU_MEM_HOST, &summary))) return err;
+    j.summary = summary != nullptr;
     return enqueue(ctx, j);
 }
 
@@ -1087,6 +1111,27 @@ int collect_thumbnails(bool discard)
     if (cur >= 0) (void)hipSetDevice(cur);
     return rc;
 }
+// Likewise for the summary counters: max-merged into the calling thread's armed HOST counters.
+int collect_summaries(bool discard)
+{
+    uint32_t* counters = discard ? nullptr : summary_host_counters();
+    int cur = -1, rc = 0;
+    uint32_t tmp[AVIFGPU_SUMMARY_COUNTERS];
+    for (int i = 0; i < context_count(); ++i) {
+        Ctx* c = ctx_at(i);
+        if (!c->d_summary || !c->summary_dirty.load(std::memory_order_acquire)) continue;
+        if (cur == -1 && hipGetDevice(&cur) != hipSuccess) { (void)hipGetLastError(); cur = -2; }
+        hipError_t e = hipSetDevice(c->device);
+        if (e == hipSuccess) e = hipMemcpy(tmp, c->d_summary, sizeof(tmp), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemsetAsync(c->d_summary, 0, sizeof(tmp), nullptr);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);        // the slots' streams do not wait for the default stream
+        if (e != hipSuccess) { if (!rc) rc = hip_fail(e, "summary read-back", AVIFGPU_writErr); continue; }
+        c->summary_dirty.store(false, std::memory_order_release);
+        if (counters) for (int k = 0; k < AVIFGPU_SUMMARY_COUNTERS; ++k) counters[k] = std::max(counters[k], tmp[k]);
+    }
+    if (cur >= 0) (void)hipSetDevice(cur);
+    return rc;
+}
 int wait_all_impl(bool discard_hist);
 }
 int wait_all() { return wait_all_impl(false); }
@@ -1110,6 +1155,8 @@ int wait_all_impl(bool discard_hist)
     int hrc = collect_histograms(discard_hist || first != 0);
     const int trc = collect_thumbnails(discard_hist || first != 0);
     if (!hrc) hrc = trc;
+    const int src = collect_summaries(discard_hist || first != 0);
+    if (!hrc) hrc = src;
     if (first) set_error(msg);
     return first ? first : hrc;
 }

@@ -70,6 +70,16 @@ void thumbnail_rows_of_tile(const avifgpu_write_desc* d, const WriteGeom& g, int
 hipError_t launch_thumbnail(const avifgpu_write_desc* d, const WriteGeom& g, int row0, int nrows, const uint8_t* const planes[4],
                             const int64_t stride[4], int tw, int th, unsigned long long* sums, hipStream_t st, int twin = 0);   // twin: avifgpu_probe_thumbnail
 
+// ---- summary_kernels.hip: the summary of a save's written planes (avifgpu_summary_attach) ----------------------------
+// The calling thread's arming for a write of `mem_kind`: 0 and *counters (nullptr: nothing armed), or formatBadParameters with a
+// message when the memory kind disagrees.
+int  summary_for_call(int mem_kind, uint32_t** counters);
+uint32_t* summary_host_counters();                   // the calling thread's armed HOST counters, or nullptr
+// Raise counters[AVIFGPU_SUMMARY_COUNTERS] by the output codes of one tile, enqueued behind the tile's launch_write(): `planes` / `stride`
+// are the pointers that kernel wrote through (at row row0; chroma: row0 >> ys), counters lives on the stream's device.
+hipError_t launch_summary(const avifgpu_write_desc* d, const WriteGeom& g, int row0, int nrows, const uint8_t* const planes[4],
+                          const int64_t stride[4], uint32_t* counters, hipStream_t st, int twin = 0);   // twin: avifgpu_probe_summary
+
 // ---- orient_kernels.hip: irot / imir orientation of an open (avifgpu_read_rows_oriented) ------------------------------
 void release_orient_staging();                       // the host path's two staging slots (avifgpu_shutdown); nothing to do if never used
 
@@ -121,6 +131,7 @@ int  read_tile_enqueue(int ctx, int slot, const avifgpu_read_desc* d, int row0, 
 int  wait_slot(int ctx, int slot);                   // the tile last queued on (ctx, slot) has fully landed in host memory
 int  wait_all();                                     // every context idle; returns the first error any tile produced.  Tiles that counted into their
                                                      // contexts' code histograms: the sums are added to `hist_bins` of the calling thread (nothing on an error)
+                                                     // (thumbnail sums and summary counters likewise: added / max-merged into the calling thread's, nothing on an error)
 // One host-pointer conversion (whole-range call or a shim save / open) at a time per process: they share slots and error state.
 void host_call_lock();
 void host_call_unlock();

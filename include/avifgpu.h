@@ -399,6 +399,65 @@ int32_t avifgpu_thumbnail_from_sums(const avifgpu_write_desc* desc, int32_t tw, 
 int32_t avifgpu_probe_thumbnail(const avifgpu_write_desc* desc, int32_t twin, int32_t tw, int32_t th, const void* const planes[4],
                                 const int64_t stride[4], uint64_t* sums, void* stream);
 
+/* ---- summary of a save: the range of every written channel, and whether R, G and B ever differ ---------------------------------
+ * An extension: what an adapter wants to know before it hands the planes to the encoder -- does the alpha plane say anything, does the
+ * chroma?  Taken from the OUTPUT of a save like the thumbnail, by a kernel of its own behind the conversion of the same rows.  Channels
+ * are in the thumbnail's order, R,G,B[,A] | Y[,A] | Y,Cb,Cr[,A], C = desc->planes.  The counters, 32-bit unsigned:
+ *     counters[0 + c] = hi[c]     = max(code)             of channel c
+ *     counters[4 + c] = lo_inv[c] = max(65535 - code)     so that the smallest code is 65535 - lo_inv[c]
+ *     counters[8]     = spread    = max over pixels of max(R,G,B) - min(R,G,B)
+ *     counters[9..15]             reserved, zero
+ * The spread is defined for colour saves in AVIFGPU_OUT_REFERENCE form (from the interleaved pixel) and for AVIFGPU_OUT_YCBCR with
+ * AVIFGPU_MATRIX_RGB_GBR (the three planes are copies of G, B, R at 4:4:4); it stays 0 everywhere else.
+ * Every counter is a RUNNING MAXIMUM.  So an all-zero block (calloc, hipMemset 0) is the empty summary; two summaries merge by an
+ * element-wise max; the result is the same for every tiling, every number of bound devices, every launch shape, pinned or pageable
+ * memory, HOST or DEVICE pointers; feeding a row twice changes nothing -- and therefore A PARTIAL FEED CANNOT BE DETECTED: the facts
+ * hold for the rows that were fed.  A channel that was fed has lo_inv > 0 (codes are at most 4095).
+ *
+ * Arm (counters != NULL) or disarm (NULL: always succeeds) the calling thread.  counters holds AVIFGPU_SUMMARY_COUNTERS words and is
+ * never cleared by the library.  While armed, every avifgpu_write_rows* call of this thread, at any depth, folds its rows' output codes
+ * in; reads are unaffected.  The FormatRecord shim's saves run on the caller's thread and honour it with mem_kind HOST.  mem_kind says
+ * where the counters live and must equal the mem_kind of the calls: HOST -- the counters are complete when each call returns (a call that
+ * fails adds nothing); DEVICE -- the kernel is enqueued on the call's stream behind the conversion, it reads the caller's dst planes
+ * and raises the caller's device counters.  A call whose mem_kind differs fails with formatBadParameters before anything is launched or
+ * queued.  A code histogram and a thumbnail may be armed at the same time.  Host-only bookkeeping: needs no device. */
+enum { AVIFGPU_SUMMARY_COUNTERS = 16 };
+int32_t avifgpu_summary_attach(uint32_t* counters, int32_t mem_kind);
+
+enum {
+    AVIFGPU_ADVICE_DROP_ALPHA = 1,   /* every alpha code is the maximum: the alpha item says nothing */
+    AVIFGPU_ADVICE_MONOCHROME = 2    /* a colour save whose content is neutral: it can be encoded without chroma */
+};
+typedef struct avifgpu_save_summary {
+    int32_t channels;         /* desc->planes */
+    int32_t min_code[4];
+    int32_t max_code[4];
+    int32_t spread;           /* -1: not applicable */
+    int32_t alpha_opaque;     /* 1: the smallest alpha code is 2^bit_depth - 1; -1: no alpha */
+    int32_t alpha_clear;      /* 1: every alpha code is 0; -1: no alpha */
+    int32_t neutral;          /* 0 | 1 */
+    int32_t advice;           /* AVIFGPU_ADVICE_* bits */
+} avifgpu_save_summary;
+
+/* Host only, integer arithmetic.  neutral: gray saves 1; REFERENCE colour and G,B,R planes spread == 0; YCBCR with
+ * AVIFGPU_CHROMA_ZERO_LIBHEIF min == max == 1 << (bit_depth - 1) on both chroma planes (R = G = B gives exactly that code); YCBCR with
+ * AVIFGPU_CHROMA_ZERO_DECODER both chroma planes within [2^(bit_depth-1) - 1, 2^(bit_depth-1)] -- that zero point is the half-integer
+ * (2^bit_depth - 1) / 2, R = G = B lands on either neighbour, so this rule says NEUTRAL TO WITHIN THE QUANTISER, not exactly grey.
+ * advice: DROP_ALPHA when alpha_opaque, MONOCHROME when a colour save is neutral.  formatBadParameters when a channel of the descriptor
+ * was never fed (lo_inv 0), or when a maximum exceeds 2^bit_depth - 1 (the counters are not of this descriptor); out is then untouched. */
+int32_t avifgpu_summary_read(const avifgpu_write_desc* desc, const uint32_t* counters, avifgpu_save_summary* out);
+
+/* Host only.  into[k] = max(into[k], from[k]) over the AVIFGPU_SUMMARY_COUNTERS words: for ranks and threads that saved row tiles of
+ * one image. */
+int32_t avifgpu_summary_merge(uint32_t* into, const uint32_t* from);
+
+/* Measuring aid (tools/bench_summary.py): launch the summary kernel ALONE on the whole frame's output planes at device pointers
+ * `planes` (as avifgpu_write_rows wrote them: the same plane use, strides in bytes), into device counters, on `stream`.  twin 0 = the
+ * kernel itself (the same counters an armed avifgpu_write_rows leaves); 1 = its atomics-free twin for attribution (the loads and the
+ * register work only: counters is left alone). */
+int32_t avifgpu_probe_summary(const avifgpu_write_desc* desc, int32_t twin, const void* const planes[4], const int64_t stride[4],
+                              uint32_t* counters, void* stream);
+
 /*
  * Inverse direction.  src[i] / src_stride[i] are what heif_image_get_plane_readonly returns
  * (ReadHeifImage.cpp:104-111) advanced to row `row0` (chroma: row0 >> yShift); plane order is
