@@ -977,13 +977,13 @@ static hipError_t launch_read_one(const ReadParams& p, hipStream_t st, char* lab
     constexpr int NCHL = (CS == kCsMono ? 1 : 3) + (ALPHA ? 1 : 0);
     constexpr int ND_OUT = PXT * NCHL * (DEPTH / 8) / 4;
     const long long waves = (long long)(((p.width + PXT - 1) / PXT + 63) / 64) * ((p.nrows + (1 << YS) - 1) >> YS);
-    long long blocks = (waves + kRpxWaves - 1) / kRpxWaves;
+    const long long need = (waves + kRpxWaves - 1) / kRpxWaves;
     // Grid cap, measured (profiles/r01/ab_read_variants.txt, second table): with the tables copied from the device cache
     // instead of rebuilt per workgroup, a 16k-block grid beats 2k by 5-10 % on the f32 and 10-bit kernels.
 #ifndef AG_READ_BLOCK_CAP
 #define AG_READ_BLOCK_CAP (256LL * 128)  /* round 5, fresh data: 32k blocks +2-3 % over 16k on the 4:4:4 opens and at 16384^2, 128k -4 % where tables are copied per block (profiles/r05/read_grid_cap_fresh_data.txt) */
 #endif
-    if (blocks > AG_READ_BLOCK_CAP) blocks = AG_READ_BLOCK_CAP;
+    const long long blocks = capped_blocks(need, AG_READ_BLOCK_CAP, hot_variant());
     const size_t lut_bytes = p.bits <= 12 ? (size_t)read_table_count(CS == kCsYcc, CS == kCsMono, ALPHA, DEPTH, p.full_range != 0, p.identity_lut != 0, p.premultiplied != 0) *
                                                 (1u << p.bits) * sizeof(float) : 0;
     uintptr_t bits = reinterpret_cast<uintptr_t>(p.dst) | (uintptr_t)p.dst_row_bytes;
@@ -1001,6 +1001,7 @@ static hipError_t launch_read_one(const ReadParams& p, hipStream_t st, char* lab
     const size_t lds = lut_bytes + ((aligned && ND_OUT > 4) ? (size_t)kRpxWaves * WaveSpan<ND_OUT>::STRIP_DW * sizeof(uint32_t) : 0);
     snprintf(label, kLabelBytes, "read_px<cs=%d,depth=%d,alpha=%d,xs=%d,ys=%d,transfer=%d,aligned=%d>", CS, DEPTH, (int)ALPHA, XS, YS,
              TRANSFER, (int)aligned);
+    label_cap(label, blocks, need, AG_READ_BLOCK_CAP);
     ReadParams q = p;
     const bool arith = p.full_range && p.bits <= 12 && read_arith_policy<CS, DEPTH, ALPHA, XS, YS>();
     if (lut_bytes && (!arith || p.twin)) {                    // (the twin keeps the table copy of the tabled form: the heavier pattern)
@@ -1094,7 +1095,7 @@ hipError_t launch_read(const ReadParams& p, int colorspace, int depth, bool alph
     const int ssz = p.bits > 8 ? 2 : 1;
     const int nch = (colorspace == AVIFGPU_COLORSPACE_MONOCHROME ? 1 : 3) + (alpha ? 1 : 0);
     const bool h422 = xs == 1 && ys == 0 && (p.width & 1) == 0 && colorspace == AVIFGPU_COLORSPACE_YCBCR;     // 4:2:2: sub-sampled along the row only
-    bool flat = AG_READ_FLAT && hot_variant() != 0 && !(hot_variant() & 16) && p.nrows > 1 && ys == 0 && (xs == 0 || h422) && px < (1LL << 29) &&
+    bool flat = AG_READ_FLAT && (hot_variant() & 0xff) != 0 && !(hot_variant() & 16) && p.nrows > 1 && ys == 0 && (xs == 0 || h422) && px < (1LL << 29) &&
                 p.dst_row_bytes == (long long)p.width * nch * (depth / 8);
     auto plane_px = [&](int pl, long long w) { return (h422 && (pl == 1 || pl == 2)) ? w / 2 : w; };
     for (int pl = 0; pl < 4 && flat; ++pl) if (p.src[pl]) flat = p.src_stride[pl] == plane_px(pl, p.width) * ssz;

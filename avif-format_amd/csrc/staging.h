@@ -6,6 +6,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
+#include <string.h>
 
 #include "../../include/avifgpu.h"
 #include "kernel_params.h"
@@ -52,6 +54,23 @@ void read_plane_extent(const avifgpu_read_desc* d, const ReadGeom& g, int plane,
 bool read_plane_used(const avifgpu_read_desc* d, const ReadGeom& g, int plane);
 
 int  hot_variant();
+// Workgroups of a capped launch: `need` = those of a launch in which every wave makes one trip of its grid-stride loop, `cap` = the
+// launcher's own compile-time cap.  Bits 8.. of the tuning word (kernel_params.h) lower the grid further and never raise it: with them
+// the tests make every wave take several trips on a tile of a few thousand pixels.  Zero there: exactly min(need, cap).
+inline long long capped_blocks(long long need, long long cap, int word)
+{
+    long long blocks = need < cap ? need : cap;
+    const long long asked = (long long)(word >> 8);
+    if (asked > 0 && asked < blocks) blocks = asked;
+    return blocks < 1 ? 1 : blocks;
+}
+// The launch label says so when the word lowered the grid: " cap=N/M", N workgroups launched where one trip per wave takes M.
+inline void label_cap(char* label, long long launched, long long need, long long cap)
+{
+    if (launched >= need || launched >= cap || strstr(label, " cap=") != nullptr) return;
+    const size_t n = strlen(label);
+    if (n < (size_t)kLabelBytes) snprintf(label + n, kLabelBytes - n, " cap=%lld/%lld", launched, need);
+}
 // The calling thread's armed code histogram (avifgpu_histogram_attach): for a depth-32 write of `mem_kind`, 0 and *bins = the armed
 // counters (nullptr: nothing armed, or the descriptor is not counted), or formatBadParameters with a message when bit depth or memory kind disagree.
 int  histogram_for_call(const avifgpu_write_desc* d, int mem_kind, uint64_t** bins);

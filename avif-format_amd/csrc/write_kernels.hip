@@ -3485,18 +3485,23 @@ __global__ __launch_bounds__(AG_COPY_BLOCK) void write_copy_rows_stream(const Co
 #ifndef AG_STREAM_BLOCK_CAP
 #define AG_STREAM_BLOCK_CAP (256LL * 512)     // grid cap of the streaming kernels (grid-stride beyond it); see AG_WRITE_BLOCK_CAP
 #endif
-static inline int grid_for(long long threads_needed)
-{
-    long long blocks = (threads_needed + AG_WPX_BLOCK - 1) / AG_WPX_BLOCK;
 #ifndef AG_WRITE_BLOCK_CAP
 #define AG_WRITE_BLOCK_CAP (256LL * 512)
 #endif
+// Workgroups of a write_px launch under the compile-time cap `cap` and the tuning word's (capped_blocks, staging.h); `label` is the
+// launch's finished label and gains " cap=N/M" when the word lowered the grid.
+static inline int grid_capped(long long threads_needed, long long cap, char* label)
+{
+    const long long need = (threads_needed + AG_WPX_BLOCK - 1) / AG_WPX_BLOCK;
+    const long long blocks = capped_blocks(need, cap, hot_variant());
+    label_cap(label, blocks, need, cap);
+    return (int)blocks;
+}
+static inline int grid_for(long long threads_needed, char* label)
+{
     // 8192^2 frames are indifferent to 16k...128k blocks; 16384^2 frames are not (RGB16 -> 12-bit 4:4:4: 0.684 ms at 16k,
     // 0.543 ms at 128k -- profiles/r01/ab_write_variants.txt): keep a wave's grid-stride loop short
-    const long long cap = AG_WRITE_BLOCK_CAP;
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    return (int)blocks;
+    return grid_capped(threads_needed, AG_WRITE_BLOCK_CAP, label);
 }
 
 // The parametric ICC variants set up ~60 wave-uniform parameters (and their pow table) per workgroup: a capped grid lets a wave
@@ -3504,10 +3509,9 @@ static inline int grid_for(long long threads_needed)
 #ifndef AG_ICC_BLOCK_CAP
 #define AG_ICC_BLOCK_CAP (256LL * 32)      /* 8192^2: 0.405 ms uncapped, 0.390 at 16k, 0.371 at 8k / 4k, 0.388 at 2k, 0.416 at 1k blocks (variant 2) */
 #endif
-static inline int grid_icc(long long threads_needed)
+static inline int grid_icc(long long threads_needed, char* label)
 {
-    const long long b = grid_for(threads_needed);
-    return (int)(b > AG_ICC_BLOCK_CAP ? AG_ICC_BLOCK_CAP : b);
+    return grid_capped(threads_needed, AG_ICC_BLOCK_CAP < AG_WRITE_BLOCK_CAP ? AG_ICC_BLOCK_CAP : AG_WRITE_BLOCK_CAP, label);
 }
 
 // A workgroup of the generic kernel that evaluates PQ in its close form starts by copying the 4-KiB exponent table to LDS: at one footprint
@@ -3518,10 +3522,9 @@ static inline int grid_icc(long long threads_needed)
 #define AG_PQ_TABLE_BLOCK_CAP (256LL * 32)
 #endif
 template <int TRANSFER>
-static inline int grid_px(long long threads_needed)
+static inline int grid_px(long long threads_needed, char* label)
 {
-    const long long b = grid_for(threads_needed);
-    return (int)((TRANSFER == kTransferPqHi && b > AG_PQ_TABLE_BLOCK_CAP) ? AG_PQ_TABLE_BLOCK_CAP : b);
+    return grid_capped(threads_needed, (TRANSFER == kTransferPqHi && AG_PQ_TABLE_BLOCK_CAP < AG_WRITE_BLOCK_CAP) ? AG_PQ_TABLE_BLOCK_CAP : AG_WRITE_BLOCK_CAP, label);
 }
 
 template <int DEPTH, int PLANES, int OUT, bool DST16, int XS, int YS, int TRANSFER>
@@ -3549,7 +3552,7 @@ static hipError_t launch_one(const WriteParams& p, hipStream_t st, char* label)
         if (p.icc8_s1 != nullptr) {                 // 8-bit matrix-shaper ICC transform requested
             snprintf(label, kLabelBytes, "write_px<depth=%d,planes=%d,out=%d,dst16=%d,xs=%d,ys=%d,transfer=%d,aligned=%d,icc=3>",
                      DEPTH, PLANES, OUT, (int)DST16, XS, YS, TRANSFER, (int)aligned);
-            const int blocks = grid_for(groups) > 2048 ? 2048 : grid_for(groups);     // tables are copied per block
+            const int blocks = grid_capped(groups, 2048 < AG_WRITE_BLOCK_CAP ? 2048 : AG_WRITE_BLOCK_CAP, label);     // tables are copied per block
             if (aligned) hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, true, 3>), dim3(blocks), dim3(AG_WPX_BLOCK), 0, st, p);
             else hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, false, 3>), dim3(blocks), dim3(AG_WPX_BLOCK), 0, st, p);
             return hipGetLastError();
@@ -3561,8 +3564,8 @@ static hipError_t launch_one(const WriteParams& p, hipStream_t st, char* label)
             groups = (long long)((p.width + PXT7 - 1) / PXT7) * ((p.nrows + (1 << YS) - 1) >> YS);
             snprintf(label, kLabelBytes, "write_px<depth=%d,planes=%d,out=%d,dst16=%d,xs=%d,ys=%d,transfer=%d,aligned=%d,icc=7>",
                      DEPTH, PLANES, OUT, (int)DST16, XS, YS, TRANSFER, (int)aligned);
-            if (aligned) hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, true, 7>), dim3(grid_for(groups)), dim3(AG_WPX_BLOCK), 0, st, p);
-            else hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, false, 7>), dim3(grid_for(groups)), dim3(AG_WPX_BLOCK), 0, st, p);
+            if (aligned) hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, true, 7>), dim3(grid_for(groups, label)), dim3(AG_WPX_BLOCK), 0, st, p);
+            else hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, false, 7>), dim3(grid_for(groups, label)), dim3(AG_WPX_BLOCK), 0, st, p);
             return hipGetLastError();
         }
     }
@@ -3572,8 +3575,8 @@ static hipError_t launch_one(const WriteParams& p, hipStream_t st, char* label)
             groups = (long long)((p.width + PXT5 - 1) / PXT5) * ((p.nrows + (1 << YS) - 1) >> YS);
             snprintf(label, kLabelBytes, "write_px<depth=%d,planes=%d,out=%d,dst16=%d,xs=%d,ys=%d,transfer=%d,aligned=%d,icc=5>",
                      DEPTH, PLANES, OUT, (int)DST16, XS, YS, TRANSFER, (int)aligned);
-            if (aligned) hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, true, 5>), dim3(grid_for(groups)), dim3(AG_WPX_BLOCK), 0, st, p);
-            else hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, false, 5>), dim3(grid_for(groups)), dim3(AG_WPX_BLOCK), 0, st, p);
+            if (aligned) hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, true, 5>), dim3(grid_for(groups, label)), dim3(AG_WPX_BLOCK), 0, st, p);
+            else hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, false, 5>), dim3(grid_for(groups, label)), dim3(AG_WPX_BLOCK), 0, st, p);
             return hipGetLastError();
         }
     }
@@ -3588,8 +3591,8 @@ static hipError_t launch_one(const WriteParams& p, hipStream_t st, char* label)
                          DEPTH, PLANES, OUT, (int)DST16, XS, YS, TRANSFER, (int)aligned);
                 const size_t lds = p.icc_p8_lds_words ? (size_t)((p.icc_p8_lds_words + 1) >> 1) * 4 : 0;          // <= 48 KiB
                 if (lds) snprintf(label + strlen(label), kLabelBytes - strlen(label), " lds");
-                if (aligned) hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, true, 8>), dim3(grid_for(groups)), dim3(AG_WPX_BLOCK), lds, st, p);
-                else hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, false, 8>), dim3(grid_for(groups)), dim3(AG_WPX_BLOCK), lds, st, p);
+                if (aligned) hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, true, 8>), dim3(grid_for(groups, label)), dim3(AG_WPX_BLOCK), lds, st, p);
+                else hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, false, 8>), dim3(grid_for(groups, label)), dim3(AG_WPX_BLOCK), lds, st, p);
                 return hipGetLastError();
             }
         }
@@ -3601,8 +3604,8 @@ static hipError_t launch_one(const WriteParams& p, hipStream_t st, char* label)
                          DEPTH, PLANES, OUT, (int)DST16, XS, YS, TRANSFER, (int)aligned);
                 const size_t lds = p.icc_s_lds ? (size_t)(p.icc_s_n[0] + p.icc_s_n[1] + p.icc_s_n[2]) * 4 : 0;      // <= 48 KiB
                 if (lds) snprintf(label + strlen(label), kLabelBytes - strlen(label), " lds");
-                if (aligned) hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, true, 6>), dim3(grid_for(groups)), dim3(AG_WPX_BLOCK), lds, st, p);
-                else hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, false, 6>), dim3(grid_for(groups)), dim3(AG_WPX_BLOCK), lds, st, p);
+                if (aligned) hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, true, 6>), dim3(grid_for(groups, label)), dim3(AG_WPX_BLOCK), lds, st, p);
+                else hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, false, 6>), dim3(grid_for(groups, label)), dim3(AG_WPX_BLOCK), lds, st, p);
                 return hipGetLastError();
             }
         }
@@ -3618,8 +3621,8 @@ static hipError_t launch_one(const WriteParams& p, hipStream_t st, char* label)
                 if constexpr (TRANSFER == 3) {
                     snprintf(label, kLabelBytes, "write_px<depth=%d,planes=%d,out=%d,dst16=%d,xs=%d,ys=%d,transfer=%d,aligned=%d,icc=4>",
                              DEPTH, PLANES, OUT, (int)DST16, XS, YS, TRANSFER, (int)aligned);
-                    if (aligned) hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, true, 4>), dim3(grid_icc(groups)), dim3(AG_WPX_BLOCK), 0, st, p);
-                    else hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, false, 4>), dim3(grid_icc(groups)), dim3(AG_WPX_BLOCK), 0, st, p);
+                    if (aligned) hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, true, 4>), dim3(grid_icc(groups, label)), dim3(AG_WPX_BLOCK), 0, st, p);
+                    else hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, false, 4>), dim3(grid_icc(groups, label)), dim3(AG_WPX_BLOCK), 0, st, p);
                     return hipGetLastError();
                 } else {
                     return hipErrorInvalidValue;    // rejected earlier by fill_write_params
@@ -3628,17 +3631,17 @@ static hipError_t launch_one(const WriteParams& p, hipStream_t st, char* label)
             snprintf(label, kLabelBytes, "write_px<depth=%d,planes=%d,out=%d,dst16=%d,xs=%d,ys=%d,transfer=%d,aligned=%d,icc=%d>",
                      DEPTH, PLANES, OUT, (int)DST16, XS, YS, TRANSFER, (int)aligned, linear ? 1 : 2);
             if (linear) {
-                if (aligned) hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, true, 1>), dim3(grid_px<TRANSFER>(groups)), dim3(AG_WPX_BLOCK), 0, st, p);
-                else hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, false, 1>), dim3(grid_px<TRANSFER>(groups)), dim3(AG_WPX_BLOCK), 0, st, p);
+                if (aligned) hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, true, 1>), dim3(grid_px<TRANSFER>(groups, label)), dim3(AG_WPX_BLOCK), 0, st, p);
+                else hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, false, 1>), dim3(grid_px<TRANSFER>(groups, label)), dim3(AG_WPX_BLOCK), 0, st, p);
             } else {
-                if (aligned) hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, true, 2>), dim3(grid_icc(groups)), dim3(AG_WPX_BLOCK), 0, st, p);
-                else hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, false, 2>), dim3(grid_icc(groups)), dim3(AG_WPX_BLOCK), 0, st, p);
+                if (aligned) hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, true, 2>), dim3(grid_icc(groups, label)), dim3(AG_WPX_BLOCK), 0, st, p);
+                else hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, false, 2>), dim3(grid_icc(groups, label)), dim3(AG_WPX_BLOCK), 0, st, p);
             }
             return hipGetLastError();
         }
     }
-    if (aligned) hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, true>), dim3(grid_px<TRANSFER>(groups)), dim3(AG_WPX_BLOCK), 0, st, p);
-    else hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, false>), dim3(grid_px<TRANSFER>(groups)), dim3(AG_WPX_BLOCK), 0, st, p);
+    if (aligned) hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, true>), dim3(grid_px<TRANSFER>(groups, label)), dim3(AG_WPX_BLOCK), 0, st, p);
+    else hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, false>), dim3(grid_px<TRANSFER>(groups, label)), dim3(AG_WPX_BLOCK), 0, st, p);
     return hipGetLastError();
     }
 }
@@ -3778,9 +3781,11 @@ hipError_t launch_stream_int(const WriteParams& p, int depth, int planes, bool d
         const long long waves = ((c.row_bytes + 1024 * kCopyK - 1) / (1024 * kCopyK)) * c.nrows;
         if (waves == 0) return hipSuccess;
         if (waves + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            long long blocks = (waves + kCopyWaves - 1) / kCopyWaves;
-            if (blocks > AG_STREAM_BLOCK_CAP * 4 / kCopyWaves) blocks = AG_STREAM_BLOCK_CAP * 4 / kCopyWaves;
-            snprintf(label, kLabelBytes, "write_copy_rows_stream<planes=%d>%s", planes, one ? " flat" : "");
+            const long long need = (waves + kCopyWaves - 1) / kCopyWaves;
+            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / kCopyWaves, variant);
+            snprintf(label, kLabelBytes, "write_copy_rows_stream<planes=%d>", planes);
+            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / kCopyWaves);
+            if (one) snprintf(label + strlen(label), kLabelBytes - strlen(label), " flat");
             hipLaunchKernelGGL((write_copy_rows_stream<kCopyK>), dim3((int)blocks), dim3(AG_COPY_BLOCK), 0, st, c);
             return hipGetLastError();
         }
@@ -3793,9 +3798,10 @@ hipError_t launch_stream_int(const WriteParams& p, int depth, int planes, bool d
         const long long waves = ((nv + 255) / 256) * p.nrows;
         if (waves == 0) return hipSuccess;
         if (waves + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            long long blocks = (waves + kStreamWaves - 1) / kStreamWaves;
-            if (blocks > AG_STREAM_BLOCK_CAP * 4 / kStreamWaves) blocks = AG_STREAM_BLOCK_CAP * 4 / kStreamWaves;
+            const long long need = (waves + kStreamWaves - 1) / kStreamWaves;
+            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / kStreamWaves, variant);
             snprintf(label, kLabelBytes, "write_int_ref_stream<depth=%d,planes=%d,dst16=%d>", depth, planes, (int)dst16);
+            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / kStreamWaves);
 #define AG_IREF(D, P) do { if (dst16) hipLaunchKernelGGL((write_int_ref_stream<D, P, true>), dim3((int)blocks), dim3(AG_STREAM_BLOCK), 0, st, p); \
                            else hipLaunchKernelGGL((write_int_ref_stream<D, P, false>), dim3((int)blocks), dim3(AG_STREAM_BLOCK), 0, st, p); } while (0)
             if (depth == 8) AG_IREF(8, 4);
@@ -3810,9 +3816,10 @@ hipError_t launch_stream_int(const WriteParams& p, int depth, int planes, bool d
         const long long waves = (((long long)p.width / 4 + 255) / 256) * p.nrows;
         if (waves == 0) return hipSuccess;
         if (waves + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            long long blocks = (waves + kF32RefWaves - 1) / kF32RefWaves;
-            if (blocks > AG_STREAM_BLOCK_CAP * 4 / kF32RefWaves) blocks = AG_STREAM_BLOCK_CAP * 4 / kF32RefWaves;
+            const long long need = (waves + kF32RefWaves - 1) / kF32RefWaves;
+            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / kF32RefWaves, variant);
             snprintf(label, kLabelBytes, "write_ga_stream<depth=16>");
+            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / kF32RefWaves);
             hipLaunchKernelGGL((write_ga_stream<16, AVIFGPU_TRANSFER_CLIP>), dim3((int)blocks), dim3(AG_F32_REF_BLOCK), 0, st, p);
             return hipGetLastError();
         }
@@ -3826,9 +3833,10 @@ hipError_t launch_stream_int(const WriteParams& p, int depth, int planes, bool d
         if (spans == 0) return hipSuccess;
         if (spans + 8LL * 65536 * 4 < 0x7fffffffLL) {
             const int wpb = ys ? 2 : 4;                                            // waves per workgroup
-            long long blocks = (spans + wpb - 1) / wpb;
-            if (blocks > AG_STREAM_BLOCK_CAP * 4 / wpb) blocks = AG_STREAM_BLOCK_CAP * 4 / wpb;
+            const long long need = (spans + wpb - 1) / wpb;
+            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / wpb, variant);
             snprintf(label, kLabelBytes, "write_rgb8_ycbcr_hot<xs=%d,ys=%d,nearest=%d>", xs, ys, (xs || ys) ? p.nearest : 0);
+            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / wpb);
 #define AG_R8(XS_, YS_, NR_) hipLaunchKernelGGL((write_rgb8_ycbcr_hot<XS_, YS_, NR_, (YS_ ? 2 : 4)>), dim3((int)blocks), dim3(64 * (YS_ ? 2 : 4)), 0, st, p)
             if (xs == 0) AG_R8(0, 0, false);
             else if (ys == 0) { if (p.nearest) AG_R8(1, 0, true); else AG_R8(1, 0, false); }
@@ -3846,9 +3854,10 @@ hipError_t launch_stream_int(const WriteParams& p, int depth, int planes, bool d
         if (spans == 0) return hipSuccess;
         if (spans + 8LL * 65536 * 4 < 0x7fffffffLL) {
             constexpr int wpb = AG_RGB8_16_WAVES;
-            long long blocks = (spans + wpb - 1) / wpb;
-            if (blocks > AG_STREAM_BLOCK_CAP * 4 / wpb) blocks = AG_STREAM_BLOCK_CAP * 4 / wpb;
+            const long long need = (spans + wpb - 1) / wpb;
+            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / wpb, variant);
             snprintf(label, kLabelBytes, "write_rgb8_ycbcr16_hot<xs=%d,ys=%d,nearest=%d>", xs, ys, (xs || ys) ? p.nearest : 0);
+            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / wpb);
 #define AG_R816(XS_, YS_, NR_) hipLaunchKernelGGL((write_rgb8_ycbcr16_hot<XS_, YS_, NR_, wpb>), dim3((int)blocks), dim3(64 * wpb), 0, st, p)
             if (xs == 0) AG_R816(0, 0, false);
             else if (ys == 0) { if (p.nearest) AG_R816(1, 0, true); else AG_R816(1, 0, false); }
@@ -3865,9 +3874,10 @@ hipError_t launch_stream_int(const WriteParams& p, int depth, int planes, bool d
         const long long spans = (long long)((p.width + 511) / 512) * ((p.nrows + (1 << ys) - 1) >> ys);
         if (spans == 0) return hipSuccess;
         if (spans + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            long long blocks = (spans + 3) / 4;
-            if (blocks > AG_STREAM_BLOCK_CAP) blocks = AG_STREAM_BLOCK_CAP;
+            const long long need = (spans + 3) / 4;
+            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP, variant);
             snprintf(label, kLabelBytes, "write_rgba8_ycbcra_hot<xs=%d,ys=%d,nearest=%d,premultiply=%d>", xs, ys, (xs || ys) ? p.nearest : 0, p.premultiply);
+            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP);
 #define AG_RA8(XS_, YS_, NR_) do { if (p.premultiply) hipLaunchKernelGGL((write_rgba8_ycbcra_hot<XS_, YS_, NR_, true>), dim3((int)blocks), dim3(256), 0, st, p); \
                                    else hipLaunchKernelGGL((write_rgba8_ycbcra_hot<XS_, YS_, NR_, false>), dim3((int)blocks), dim3(256), 0, st, p); } while (0)
             if (xs == 0) AG_RA8(0, 0, false);
@@ -3892,9 +3902,10 @@ hipError_t launch_stream_int(const WriteParams& p, int depth, int planes, bool d
         const long long spans = (long long)((p.width + 511) / 512) * p.nrows;
         if (spans == 0) return hipSuccess;
         if (spans + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            long long blocks = (spans + kStreamWaves * AG_RGB16_NS - 1) / (kStreamWaves * AG_RGB16_NS);
-            if (blocks > AG_STREAM_BLOCK_CAP * 4 / kStreamWaves) blocks = AG_STREAM_BLOCK_CAP * 4 / kStreamWaves;
+            const long long need = (spans + kStreamWaves * AG_RGB16_NS - 1) / (kStreamWaves * AG_RGB16_NS);
+            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / kStreamWaves, variant);
             snprintf(label, kLabelBytes, "write_rgb16_ycbcr444_hot<ns=%d%s>", AG_RGB16_NS, dst16 ? "" : ",to8");
+            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / kStreamWaves);
             if (dst16) hipLaunchKernelGGL((write_rgb16_ycbcr444_hot<AG_RGB16_NS>), dim3((int)blocks), dim3(AG_STREAM_BLOCK), 0, st, p);
             else hipLaunchKernelGGL((write_rgb16_ycbcr444_hot<AG_RGB16_NS, true>), dim3((int)blocks), dim3(AG_STREAM_BLOCK), 0, st, p);
             return hipGetLastError();
@@ -3912,9 +3923,10 @@ hipError_t launch_stream_int(const WriteParams& p, int depth, int planes, bool d
         const long long spans = (long long)((p.width + 511) / 512) * p.nrows;
         if (spans == 0) return hipSuccess;
         if (spans + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            long long blocks = (spans + kStreamWaves - 1) / kStreamWaves;
-            if (blocks > AG_STREAM_BLOCK_CAP * 4 / kStreamWaves) blocks = AG_STREAM_BLOCK_CAP * 4 / kStreamWaves;
+            const long long need = (spans + kStreamWaves - 1) / kStreamWaves;
+            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / kStreamWaves, variant);
             snprintf(label, kLabelBytes, "write_rgba16_ycbcra444_hot%s", dst16 ? "" : "<to8>");
+            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / kStreamWaves);
             if (dst16) hipLaunchKernelGGL((write_rgba16_ycbcra444_hot<false>), dim3((int)blocks), dim3(AG_STREAM_BLOCK), 0, st, p);
             else hipLaunchKernelGGL((write_rgba16_ycbcra444_hot<true>), dim3((int)blocks), dim3(AG_STREAM_BLOCK), 0, st, p);
             return hipGetLastError();
@@ -3928,9 +3940,10 @@ hipError_t launch_stream_int(const WriteParams& p, int depth, int planes, bool d
         const long long spans = (long long)((p.width + 511) / 512) * ((p.nrows + (1 << ys) - 1) >> ys);
         if (spans == 0) return hipSuccess;
         if (spans + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            long long blocks = (spans + kStreamWaves - 1) / kStreamWaves;
-            if (blocks > AG_STREAM_BLOCK_CAP * 4 / kStreamWaves) blocks = AG_STREAM_BLOCK_CAP * 4 / kStreamWaves;
+            const long long need = (spans + kStreamWaves - 1) / kStreamWaves;
+            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / kStreamWaves, variant);
             snprintf(label, kLabelBytes, "write_rgba16_ycbcra_sub_hot<ys=%d,nearest=%d%s>", ys, p.nearest, dst16 ? "" : ",to8");
+            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / kStreamWaves);
 #define AG_RA16B(YS_, T8) do { if (p.nearest) hipLaunchKernelGGL((write_rgba16_ycbcra_sub_hot<YS_, true, T8>), dim3((int)blocks), dim3(AG_STREAM_BLOCK), 0, st, p); \
                                else hipLaunchKernelGGL((write_rgba16_ycbcra_sub_hot<YS_, false, T8>), dim3((int)blocks), dim3(AG_STREAM_BLOCK), 0, st, p); } while (0)
 #define AG_RA16(YS_) do { if (dst16) AG_RA16B(YS_, false); else AG_RA16B(YS_, true); } while (0)
@@ -3950,9 +3963,10 @@ hipError_t launch_stream_int(const WriteParams& p, int depth, int planes, bool d
         const long long spans = (long long)((p.width + 511) / 512) * ((p.nrows + (1 << ys) - 1) >> ys);
         if (spans == 0) return hipSuccess;
         if (spans + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            long long blocks = (spans + kStreamWaves - 1) / kStreamWaves;
-            if (blocks > AG_STREAM_BLOCK_CAP * 4 / kStreamWaves) blocks = AG_STREAM_BLOCK_CAP * 4 / kStreamWaves;
+            const long long need = (spans + kStreamWaves - 1) / kStreamWaves;
+            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / kStreamWaves, variant);
             snprintf(label, kLabelBytes, "write_rgb16_ycbcr_sub_hot<ys=%d%s>", ys, dst16 ? "" : ",to8");
+            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / kStreamWaves);
             if (dst16) { if (ys) hipLaunchKernelGGL((write_rgb16_ycbcr_sub_hot<1>), dim3((int)blocks), dim3(AG_STREAM_BLOCK), 0, st, p);
                          else hipLaunchKernelGGL((write_rgb16_ycbcr_sub_hot<0>), dim3((int)blocks), dim3(AG_STREAM_BLOCK), 0, st, p); }
             else { if (ys) hipLaunchKernelGGL((write_rgb16_ycbcr_sub_hot<1, true>), dim3((int)blocks), dim3(AG_STREAM_BLOCK), 0, st, p);
@@ -3974,9 +3988,10 @@ hipError_t launch_stream_f32_sub_rgba(const WriteParams& p, int depth, int plane
         const long long waves = (((long long)p.width / 2 + 255) / 256) * p.nrows;
         if (waves == 0) return hipSuccess;
         if (waves + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            long long blocks = (waves + kF32RefWaves - 1) / kF32RefWaves;
-            if (blocks > AG_STREAM_BLOCK_CAP * 4 / kF32RefWaves) blocks = AG_STREAM_BLOCK_CAP * 4 / kF32RefWaves;
+            const long long need = (waves + kF32RefWaves - 1) / kF32RefWaves;
+            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / kF32RefWaves, variant);
             snprintf(label, kLabelBytes, "write_ga_stream<depth=32,transfer=%d>", p.transfer);
+            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / kF32RefWaves);
             if (p.transfer == AVIFGPU_TRANSFER_PQ) {
                 if (pq_hi_launch(p)) hipLaunchKernelGGL((write_ga_stream<32, kTransferPqHi>), dim3((int)blocks), dim3(AG_F32_REF_BLOCK), 0, st, p);
                 else hipLaunchKernelGGL((write_ga_stream<32, AVIFGPU_TRANSFER_PQ>), dim3((int)blocks), dim3(AG_F32_REF_BLOCK), 0, st, p);
@@ -3995,9 +4010,10 @@ hipError_t launch_stream_f32_sub_rgba(const WriteParams& p, int depth, int plane
         const long long spans = (long long)((p.width + 255) / 256) * ((p.nrows + (1 << ys) - 1) >> ys);
         if (spans == 0) return hipSuccess;
         if (spans + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            long long blocks = (spans + kRgbaWaves - 1) / kRgbaWaves;
-            if (blocks > AG_RGBA_BLOCK_CAP * 4 / kRgbaWaves) blocks = AG_RGBA_BLOCK_CAP * 4 / kRgbaWaves;
+            const long long need = (spans + kRgbaWaves - 1) / kRgbaWaves;
+            const long long blocks = capped_blocks(need, AG_RGBA_BLOCK_CAP * 4 / kRgbaWaves, variant);
             snprintf(label, kLabelBytes, "write_rgba32_ycbcra_sub_hot<transfer=%d,xs=1,ys=%d,nearest=%d>", p.transfer, ys, p.nearest);
+            label_cap(label, blocks, need, AG_RGBA_BLOCK_CAP * 4 / kRgbaWaves);
 #define AG_RSUB3(TR, YS_, NR_) hipLaunchKernelGGL((write_rgba32_ycbcra_sub_hot<TR, YS_, NR_>), dim3((int)blocks), dim3(AG_RGBA_STREAM_BLOCK), 0, st, p)
 #define AG_RSUB2(TR, YS_) do { if (p.nearest) AG_RSUB3(TR, YS_, true); else AG_RSUB3(TR, YS_, false); } while (0)
 #define AG_RSUB(TR) do { if (ys) AG_RSUB2(TR, 1); else AG_RSUB2(TR, 0); } while (0)
@@ -4028,9 +4044,10 @@ hipError_t launch_stream_f32_sub_rgba(const WriteParams& p, int depth, int plane
         const long long spans = (long long)((p.width + 64 * AG_RGBA_HOT_PXL - 1) / (64 * AG_RGBA_HOT_PXL)) * p.nrows;
         if (spans == 0) return hipSuccess;
         if (spans + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            long long blocks = (spans + kRgbaWaves - 1) / kRgbaWaves;
-            if (blocks > AG_RGBA_BLOCK_CAP * 4 / kRgbaWaves) blocks = AG_RGBA_BLOCK_CAP * 4 / kRgbaWaves;
+            const long long need = (spans + kRgbaWaves - 1) / kRgbaWaves;
+            const long long blocks = capped_blocks(need, AG_RGBA_BLOCK_CAP * 4 / kRgbaWaves, variant);
             snprintf(label, kLabelBytes, "write_rgba32_ycbcra444_hot<transfer=%d>%s", p.transfer, rgba_icc1 ? " icc=1" : rgba_icc4 ? " icc=4" : rgba_icc2 ? " icc=2" : "");
+            label_cap(label, blocks, need, AG_RGBA_BLOCK_CAP * 4 / kRgbaWaves);
             if (rgba_icc4) { hipLaunchKernelGGL((write_rgba32_ycbcra444_hot<AVIFGPU_TRANSFER_CLIP, 4>), dim3((int)blocks), dim3(AG_RGBA_STREAM_BLOCK), 0, st, p); return hipGetLastError(); }
 #define AG_RGBA(TR) do { if (rgba_icc1) hipLaunchKernelGGL((write_rgba32_ycbcra444_hot<TR, 1>), dim3((int)blocks), dim3(AG_RGBA_STREAM_BLOCK), 0, st, p); \
                          else if (rgba_icc2) hipLaunchKernelGGL((write_rgba32_ycbcra444_hot<TR, 2>), dim3((int)blocks), dim3(AG_RGBA_STREAM_BLOCK), 0, st, p); \
@@ -4058,9 +4075,10 @@ hipError_t launch_stream_f32_sub_rgba(const WriteParams& p, int depth, int plane
         if (spans == 0) return hipSuccess;
         if (spans + 8LL * 65536 * 4 < 0x7fffffffLL) {
             const int spw = (AG_SUB_SPW2 && ys == 0 && (p.width % 512) == 0 && spans >= AG_SUB_SPW2_MIN_SPANS) ? 2 : 1;      // spans per wave (see the kernel's loop)
-            long long blocks = (spans + kF32Waves * spw - 1) / (kF32Waves * spw);
-            if (blocks > AG_STREAM_BLOCK_CAP * 4 / kF32Waves) blocks = AG_STREAM_BLOCK_CAP * 4 / kF32Waves;
+            const long long need = (spans + kF32Waves * spw - 1) / (kF32Waves * spw);
+            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / kF32Waves, variant);
             snprintf(label, kLabelBytes, "write_rgb32_ycbcr_sub_hot<transfer=%d,xs=1,ys=%d>%s", p.transfer, ys, icc1 ? " icc=1" : icc4 ? " icc=4" : icc2 ? " icc=2" : "");
+            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / kF32Waves);
 #define AG_SUB3(TR, YS_, IC) do { if (p.nearest) hipLaunchKernelGGL((write_rgb32_ycbcr_sub_hot<TR, 1, YS_, IC, true>), dim3((int)blocks), dim3(AG_F32_STREAM_BLOCK), 0, st, p); \
                                   else hipLaunchKernelGGL((write_rgb32_ycbcr_sub_hot<TR, 1, YS_, IC, false>), dim3((int)blocks), dim3(AG_F32_STREAM_BLOCK), 0, st, p); } while (0)
 #define AG_SUB2(TR, YS_) do { if (icc1) AG_SUB3(TR, YS_, 1); else if (icc2) AG_SUB3(TR, YS_, 2); else AG_SUB3(TR, YS_, 0); } while (0)
@@ -4355,8 +4373,7 @@ hipError_t launch_write_hist(const WriteParams& p0, int planes, unsigned long lo
     }
     const long long waves = (((long long)p.width + kHistPxt - 1) / kHistPxt + 63) / 64 * p.nrows;
     if (waves >= 0x7fffffffLL - (long long)kHistMaxBlocks * kHistWaves) return hipErrorInvalidValue;       // 32-bit wave index in the kernel
-    long long blocks = (waves + kHistWaves - 1) / kHistWaves;
-    if (blocks > kHistMaxBlocks) blocks = kHistMaxBlocks;
+    const long long blocks = capped_blocks((waves + kHistWaves - 1) / kHistWaves, kHistMaxBlocks, hot_variant());      // (no label of its own)
     const bool aligned = ((reinterpret_cast<uintptr_t>(p.src) | (uintptr_t)p.src_row_bytes) & 15) == 0;
     const HistParams h = { bins, p.maxv + 1 };
     if (twin) {                                            // the timing twins: aligned RGB rows, PQ, no profile
@@ -4417,7 +4434,7 @@ static hipError_t launch_write_impl(const WriteParams& p, int depth, int planes,
 {
     // hot path: RGB f32 (no alpha) -> YCbCr 4:4:4 u16 with aligned rows; `variant` is a tuning word:
     //   bit0 enable, bit1 PXL=8 (else 4), bit2 non-temporal, bit3 take the size-gated streaming kernels at any size (tests);
-    //   bits 8.. = blocks (0 = default).
+    //   bits 8.. = a block cap below the launcher's own, for every capped launch of the library (0 = none; capped_blocks, staging.h).
     // (8-bit documents stay on write_px: measured 0.057 vs 0.069 ms for the RGB8 copy, 0.090 vs 0.095 ms for RGBA8 premultiplied)
     {   // 8- and 16-bit documents: part 2; f32 documents saved 4:2:2 / 4:2:0 or with transparency: part 3; the rest of this function: part 1
         bool taken = false;
@@ -4435,9 +4452,10 @@ static hipError_t launch_write_impl(const WriteParams& p, int depth, int planes,
             const long long spans = (long long)((p.width + 511) / 512) * p.nrows;
             if (spans == 0) return hipSuccess;
             if (spans + 8LL * 65536 * 4 < 0x7fffffffLL) {
-                long long blocks = (spans + kF32Waves - 1) / kF32Waves;
-                if (blocks > AG_STREAM_BLOCK_CAP * 4 / kF32Waves) blocks = AG_STREAM_BLOCK_CAP * 4 / kF32Waves;
+                const long long need = (spans + kF32Waves - 1) / kF32Waves;
+                const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / kF32Waves, variant);
                 snprintf(label, kLabelBytes, "write_rgb32_icc1_ycbcr444_hot<transfer=%d,out=ref> icc=%d", p.transfer, r4 ? 4 : r2 ? 2 : 1);
+                label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / kF32Waves);
                 if (r4) { hipLaunchKernelGGL((write_rgb32_icc1_ycbcr444_hot<AVIFGPU_TRANSFER_CLIP, 4, true>), dim3((int)blocks), dim3(AG_F32_STREAM_BLOCK), 0, st, p); return hipGetLastError(); }
 #define AG_IREF32(TR) do { if (r2) hipLaunchKernelGGL((write_rgb32_icc1_ycbcr444_hot<TR, 2, true>), dim3((int)blocks), dim3(AG_F32_STREAM_BLOCK), 0, st, p); \
                            else hipLaunchKernelGGL((write_rgb32_icc1_ycbcr444_hot<TR, 1, true>), dim3((int)blocks), dim3(AG_F32_STREAM_BLOCK), 0, st, p); } while (0)
@@ -4461,9 +4479,10 @@ static hipError_t launch_write_impl(const WriteParams& p, int depth, int planes,
         const long long waves = ((n4 + 255) / 256) * p.nrows;
         if (waves == 0) return hipSuccess;
         if (waves + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            long long blocks = (waves + kF32RefWaves - 1) / kF32RefWaves;
-            if (blocks > AG_STREAM_BLOCK_CAP * 4 / kF32RefWaves) blocks = AG_STREAM_BLOCK_CAP * 4 / kF32RefWaves;
+            const long long need = (waves + kF32RefWaves - 1) / kF32RefWaves;
+            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / kF32RefWaves, variant);
             snprintf(label, kLabelBytes, "write_f32_ref_stream<transfer=%d,planes=%d>", p.transfer, planes);
+            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / kF32RefWaves);
 #define AG_REF(TR) do { if (planes == 4) hipLaunchKernelGGL((write_f32_ref_stream<TR, 4>), dim3((int)blocks), dim3(AG_F32_REF_BLOCK), 0, st, p); \
                         else if (planes == 1) hipLaunchKernelGGL((write_f32_ref_stream<TR, 1>), dim3((int)blocks), dim3(AG_F32_REF_BLOCK), 0, st, p); \
                         else hipLaunchKernelGGL((write_f32_ref_stream<TR, 3>), dim3((int)blocks), dim3(AG_F32_REF_BLOCK), 0, st, p); } while (0)
@@ -4490,9 +4509,10 @@ static hipError_t launch_write_impl(const WriteParams& p, int depth, int planes,
         const long long spans = (long long)((p.width + 511) / 512) * p.nrows;
         if (spans == 0) return hipSuccess;
         if (spans + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            long long blocks = (spans + kF32Waves - 1) / kF32Waves;
-            if (blocks > AG_STREAM_BLOCK_CAP * 4 / kF32Waves) blocks = AG_STREAM_BLOCK_CAP * 4 / kF32Waves;
+            const long long need = (spans + kF32Waves - 1) / kF32Waves;
+            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / kF32Waves, variant);
             snprintf(label, kLabelBytes, "write_rgb32_icc1_ycbcr444_hot<transfer=%d> icc=%d", p.transfer, icc4 ? 4 : icc2 ? 2 : 1);
+            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / kF32Waves);
             if (icc4) { hipLaunchKernelGGL((write_rgb32_icc1_ycbcr444_hot<AVIFGPU_TRANSFER_CLIP, 4>), dim3((int)blocks), dim3(AG_F32_STREAM_BLOCK), 0, st, p); return hipGetLastError(); }
 #define AG_I444(TR) do { if (icc2) hipLaunchKernelGGL((write_rgb32_icc1_ycbcr444_hot<TR, 2>), dim3((int)blocks), dim3(AG_F32_STREAM_BLOCK), 0, st, p); \
                          else hipLaunchKernelGGL((write_rgb32_icc1_ycbcr444_hot<TR, 1>), dim3((int)blocks), dim3(AG_F32_STREAM_BLOCK), 0, st, p); } while (0)
@@ -4517,10 +4537,11 @@ static hipError_t launch_write_impl(const WriteParams& p, int depth, int planes,
             if (spans == 0) return hipSuccess;
             if (spans + 8LL * 65536 * 4 < 0x7fffffffLL) {
             constexpr int WPB = kHot444Waves;
-            long long blocks = (spans + WPB - 1) / WPB;
-            const long long cap = (variant >> 8) ? (variant >> 8) : 256LL * 512 * 4 / WPB;   // 8192^2: one span per wave measured 5-6 % faster than two
-            if (blocks > cap) blocks = cap;
+            const long long need = (spans + WPB - 1) / WPB;
+            const long long cap = 256LL * 512 * 4 / WPB;                                      // 8192^2: one span per wave measured 5-6 % faster than two
+            const long long blocks = capped_blocks(need, cap, variant);
             snprintf(label, kLabelBytes, "write_rgb32_ycbcr444_hot<transfer=%d,pxl=%d,nt=%d>", p.transfer, px8 ? 8 : 4, (int)nt);
+            label_cap(label, blocks, need, cap);
             // measuring knob (not a tuning word of the product): AVIFGPU_DEBUG_LDS_PAD = bytes of unused dynamic LDS per workgroup, i.e. fewer
             // resident workgroups per CU -- how the kernel's rate depends on the number of waves per SIMD (profiles/r05/occupancy_sweep_444.txt)
             // Compiled in only with -DAG_MEASURE=1 (tools/ab_variants.sh): a product launch reads no environment variable.

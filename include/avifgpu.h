@@ -589,8 +589,11 @@ int32_t avifgpu_write_plane_geometry(const avifgpu_write_desc* desc, int32_t pla
 int64_t avifgpu_write_algorithmic_bytes(const avifgpu_write_desc* desc, int32_t nrows); /* in + out */
 int64_t avifgpu_read_algorithmic_bytes(const avifgpu_read_desc* desc, int32_t nrows);
 
-/* Tuning hook for benchmarks (not part of the reference mapping): selects the implementation variant of the
- * dominant kernel; see avif-format_amd/csrc/kernel_params.h.  Results are byte-identical for every value (with an ICC transform of
+/* Tuning hook for benchmarks and tests (not part of the reference mapping): the low byte selects the implementation variant of the
+ * dominant kernel and a few A/B switches; bits 8.. , when not zero, are a number of workgroups no capped launch of the library exceeds
+ * (write, read and histogram kernels alike) -- it can only lower a grid, so that every wave walks several trips of its grid-stride loop
+ * on a small tile, and avifgpu_last_kernel_name() then carries " cap=N/M" (N workgroups launched, M for one trip per wave).  See
+ * avif-format_amd/csrc/kernel_params.h.  Results are byte-identical for every value (with an ICC transform of
  * a 32-bit document: identical within tier 2 -- the streaming kernels run the 3x3 in single precision). */
 void avifgpu_set_hot_variant(int32_t variant);
 

@@ -2,8 +2,9 @@
 three stripes of 42 rows):
  (a) every sample of every plane of the frame converted in ONE launch is compared with the CPU oracle run on the same frame on all host
      cores (oracle_write_image_all_cores: oracle_write_rows over 32-row blocks -- byte-identical to the whole-image call,
-     tests/test_oracle_properties.py).  Flat launches, the 32 k-block grid cap, > 4 GiB offsets (C5's source is 4.29 GB) and every span
-     index in between exist only at this size.  Integer documents: torch.equal on every plane.  Float documents (T2): max |dcode| <= 1,
+     tests/test_oracle_properties.py).  Flat launches, > 4 GiB offsets (C5's source is 4.29 GB) and every span index in between exist only at
+     this size; of the grid caps only C5's (16384^2 RGBA f32: two trips a wave) is reached -- the grid-stride loops themselves are walked
+     at small sizes by tests/test_zz_gpu_grid_stride.py.  Integer documents: torch.equal on every plane.  Float documents (T2): max |dcode| <= 1,
      exact >= 99.95 % at 10 bit / 99.9 % at 12 bit per plane, and EVERY mismatching sample is shown to lie within 2e-5 relative of a code
      boundary of the float64 function (for Y/Cb/Cr planes: one of the source samples the code depends on does); beyond that, every
      sample whose whole footprint is DETERMINED (tests/truth64.py, evaluated on the device in float64) equals the oracle exactly --
