@@ -45,7 +45,10 @@ def test_read_parity_host_buffers(gpu, cid, kw):
 
 
 def test_read_exhaustive_8bit_yuv(gpu):
-    """A 64^3 lattice of (Y,U,V) plus all 256 luma codes, every matrix, both ranges -- bit-exact."""
+    """A 64^3 lattice of (Y,U,V) plus all 256 luma codes, every matrix, both ranges -- bit-exact.
+    A LATTICE, not all triples: 64 evenly spaced codes per channel are 1.6 % of the 2^24 triples, 4:4:4 without alpha through one
+    kernel form (an oracle that contracts one multiply-add differs from the real one on 64 + 71 BT.709 triples, none of them on this
+    lattice).  All triples, every chroma format and both kernel instantiations: tests/test_zz_gpu_whole_domain_read.py."""
     v = np.linspace(0, 255, 64).round().astype(np.uint8)
     Y, U, V = np.meshgrid(v, v, v, indexing="ij")
     n = Y.size
@@ -132,7 +135,8 @@ def test_unpremultiply_claims_hold_on_this_device(tool, needle):
     """The two device-side proofs behind the premultiplied-alpha opens (read_kernels.hip, device_math.h): the integer-domain unpremultiply
     from one reciprocal per pixel equals the reference's float expression for every (colour, alpha) pair of 8-, 10- and 12-bit images
     (tools/divcheck_unpremul_i), and that reciprocal -- v_rcp_f32 + one Newton step -- equals IEEE 1 / A for every alpha
-    (tools/rcpcheck_alpha).  Built by the package Makefile with hipcc."""
+    (tools/rcpcheck_alpha).  Built by the package Makefile with hipcc.  (The third proof of this kind, tools/divcheck behind div_by_kg,
+    runs in tests/test_zz_gpu_whole_domain_read.py: a case added here would move every later test of the suite one place on.)"""
     import os
     import subprocess
     exe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", tool)

@@ -1,0 +1,211 @@
+"""Integer opens against the oracle on EVERY code combination their arithmetic can see, bit for bit (no tolerance anywhere).
+
+The read kernels reach the oracle's bits by other routes than its plain expressions: x / kg as three FMAs (div_by_kg), u / max as an
+FMA on a two-float reciprocal (unorm_to_float), clamp + floor + cast in one step (put_u8), pixel pairs in packed single precision
+(decode_ycc8_packed_pair), the integer-domain unpremultiply.  Each rests on a proof that ran once.  Here the product's own kernels
+run over the whole domain of each proof:
+
+  8 bit        all 2^24 (Y, Cb, Cr) triples, 4:4:4 / 4:2:2 / 4:2:0, six matrices, both ranges, aligned (flat) and unaligned planes
+  10 / 12 bit  the Latin square: every (Y, Cb), (Y, Cr), (Cb, Cr) pair -- all that R, B and the chroma term of G depend on --
+               without alpha (table-free at 4:4:4) and with straight alpha (tabled)
+  premultiplied alpha at 8 / 10 / 12 bit: every (code, alpha) pair of gray + alpha and of each channel of planar RGB + alpha; YCbCr + alpha
+               on the Latin square under an alpha plane that takes every code in every row and column
+  IEEE division (tuning bit 128) on the 12-bit Latin square and the 8-bit BT.709 triples
+
+NOT exhaustive: 10- and 12-bit TRIPLES (2^30, 2^36) -- G's final subtraction Y - term is seen for n^2 of them.
+Every case asserts from the launch label that the intended kernel form ran.  Inputs: tests/exhaustive_inputs.py, whose coverage claims
+tests/test_exhaustive_inputs.py counts; the oracle itself is held to a numpy restatement of the reference there.
+The file is named to be collected after every earlier GPU test, so that those keep their places in the collection order.
+"""
+import functools
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import exhaustive_inputs as xi
+import harness
+
+pkg = harness.pkg
+pytestmark = pytest.mark.gpu
+
+DEFAULT_VARIANT = 1 | 2 | 4
+ODD_PAD = 3                       # samples behind every plane row: odd pitches at 8 bit, 6 bytes at 16 -- never a multiple of 16
+
+CHROMA = {"444": pkg.CHROMA_444, "422": pkg.CHROMA_422, "420": pkg.CHROMA_420}
+MATRICES8 = [("bt601", pkg.MATRIX_BT601), ("bt709", pkg.MATRIX_BT709), ("bt2020ncl", pkg.MATRIX_BT2020_NCL), ("fcc", pkg.MATRIX_FCC),
+             ("smpte240m", pkg.MATRIX_SMPTE240M), ("gbr", pkg.MATRIX_RGB_GBR)]
+# the three matrices of cases.py and one chromaticity-derived row (kg of the EG 432 primaries: one of the 15 verified divisors)
+MATRICES16 = [("bt601", pkg.MATRIX_BT601, pkg.PRIMARIES_BT709), ("bt709", pkg.MATRIX_BT709, pkg.PRIMARIES_BT709),
+              ("bt2020ncl", pkg.MATRIX_BT2020_NCL, pkg.PRIMARIES_BT2020),
+              ("chromaderived432", pkg.MATRIX_CHROMA_DERIVED_NCL, pkg.PRIMARIES_SMPTE432)]
+
+
+@functools.lru_cache(maxsize=2)
+def _triples(chroma, phase):
+    return xi.all_triples_444() if chroma == "444" else xi.all_triples_sub(chroma, phase)
+
+
+@functools.lru_cache(maxsize=1)
+def _latin(bits, chroma):
+    return xi.latin_square(bits, chroma)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _release_inputs():
+    """The shared inputs (up to 200 MB) go when this file's tests are done."""
+    yield
+    _triples.cache_clear()
+    _latin.cache_clear()
+
+
+def _arith_policy(d, xs):
+    """read_arith_policy of read_kernels.hip for the integer hosts: which configurations decode without tables (full range only)."""
+    ycc, mono = d.colorspace == pkg.COLORSPACE_YCBCR, d.colorspace == pkg.COLORSPACE_MONOCHROME
+    alpha = d.alpha_state != pkg.ALPHA_NONE
+    if d.depth == 16:
+        return mono or (ycc and xs == 0 and not alpha)
+    return (ycc and alpha and xs == 1) or (mono and not alpha)
+
+
+def _assert_form(gpu, d, pad, variant=DEFAULT_VARIANT):
+    """The launch label names the kernel instantiation this case is about: name, aligned=, tables=none, flat."""
+    label = gpu.last_kernel()
+    xs, ys = harness.chroma_shift(d.chroma) if d.colorspace == pkg.COLORSPACE_YCBCR else (0, 0)
+    alpha = int(d.alpha_state != pkg.ALPHA_NONE)
+    assert label.startswith(f"read_px<cs={d.colorspace},depth={d.depth},alpha={alpha},xs={xs},ys={ys},"), label
+    assert f"aligned={int(pad == 0)}>" in label, label
+    arith = bool(d.full_range_flag) and d.bit_depth <= 12 and _arith_policy(d, xs)
+    assert (" tables=none" in label) == arith, label
+    flat = pad == 0 and ys == 0 and not (variant & 16)
+    assert label.endswith(" flat") == flat, label
+
+
+def _open_and_compare(gpu, d, planes, want, pads=(0, ODD_PAD), variant=DEFAULT_VARIANT, what=()):
+    for pad in pads:
+        got = harness.gpu_read(gpu, d, planes if pad == 0 else xi.with_stride_pad(planes, pad))
+        _assert_form(gpu, d, pad, variant)
+        if not np.array_equal(got, want):
+            bad = np.argwhere(got != want)
+            raise AssertionError((what, f"pad={pad}", gpu.last_kernel(), f"{len(bad)} samples differ", "first (row, sample): got, oracle",
+                                  [(tuple(int(v) for v in i), int(got[tuple(i)]), int(want[tuple(i)])) for i in bad[:8]]))
+
+
+def _ycc_desc(planes, chroma, bits, depth, matrix, fr, alpha=pkg.ALPHA_NONE, primaries=pkg.PRIMARIES_BT709):
+    h, w = planes[0].shape
+    return pkg.ReadDesc(width=w, height=h, colorspace=pkg.COLORSPACE_YCBCR, chroma=CHROMA[chroma], bit_depth=bits, depth=depth,
+                        alpha_state=alpha, matrix_coefficients=matrix, color_primaries=primaries, full_range_flag=fr)
+
+
+# ---- 8 bit: all triples -----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,matrix", MATRICES8, ids=[n for n, _ in MATRICES8])
+@pytest.mark.parametrize("chroma", ["444", "422", "420"])
+def test_open_all_8bit_triples(gpu, chroma, name, matrix):
+    """8-bit YCbCr -> RGB8 on all 2^24 triples: both ranges, both footprint phases of the sub-sampled forms, contiguous planes (flat
+    where the form has a flat launch, aligned instantiation) and planes with an odd pitch (unaligned instantiation)."""
+    for phase in ((0,) if chroma == "444" else (0, 1)):
+        planes = _triples(chroma, phase)
+        for fr in (1, 0):
+            d = _ycc_desc(planes, chroma, 8, 8, matrix, fr)
+            _open_and_compare(gpu, d, planes, harness.oracle_read(d, planes), what=(chroma, name, f"fr={fr}", f"phase={phase}"))
+
+
+# ---- 10 / 12 bit: the Latin square --------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("fr", [1, 0], ids=["full", "limited"])
+@pytest.mark.parametrize("name,matrix,primaries", MATRICES16, ids=[n for n, _, _ in MATRICES16])
+@pytest.mark.parametrize("chroma", ["444", "422", "420"])
+@pytest.mark.parametrize("bits", [10, 12])
+def test_open_latin_square_16bit_host(gpu, bits, chroma, name, matrix, primaries, fr):
+    """10- / 12-bit YCbCr -> 16-bit host rows on every (Y, Cb), (Y, Cr) and (Cb, Cr) pair, at every position of the chroma footprint:
+    without alpha (4:4:4 full range decodes without tables) and with straight alpha (tabled).  The 10-bit cases also run the
+    unaligned instantiation."""
+    planes = _latin(bits, chroma)
+    pads = (0, ODD_PAD) if bits == 10 else (0,)
+    d = _ycc_desc(planes, chroma, bits, 16, matrix, fr, primaries=primaries)
+    _open_and_compare(gpu, d, planes, harness.oracle_read(d, planes), pads=pads, what=(bits, chroma, name, fr, "opaque"))
+    with_alpha = dict(planes)
+    with_alpha[3] = xi.latin_alpha(bits, planes[0].shape)
+    d = _ycc_desc(planes, chroma, bits, 16, matrix, fr, alpha=pkg.ALPHA_STRAIGHT, primaries=primaries)
+    _open_and_compare(gpu, d, with_alpha, harness.oracle_read(d, with_alpha), pads=pads, what=(bits, chroma, name, fr, "straight alpha"))
+
+
+# ---- premultiplied alpha on the integer hosts ---------------------------------------------------------------------------------------
+def _host_depth(bits):
+    return 8 if bits == 8 else 16
+
+
+@pytest.mark.parametrize("bits", [8, 10, 12])
+def test_open_gray_alpha_premultiplied_every_pair(gpu, bits):
+    """Gray + premultiplied alpha: every (code, alpha) pair, both ranges (the luma table differs), aligned and unaligned."""
+    code, alpha = xi.pairs(bits)
+    planes = {0: code, 3: alpha}
+    n = 1 << bits
+    for fr in (1, 0):
+        d = pkg.ReadDesc(width=n, height=n, colorspace=pkg.COLORSPACE_MONOCHROME, chroma=pkg.CHROMA_MONOCHROME, bit_depth=bits,
+                         depth=_host_depth(bits), alpha_state=pkg.ALPHA_PREMULTIPLIED, full_range_flag=fr)
+        _open_and_compare(gpu, d, planes, harness.oracle_read(d, planes), pads=(0, ODD_PAD) if bits < 12 else (0,), what=(bits, fr))
+
+
+@pytest.mark.parametrize("bits", [8, 10, 12])
+def test_open_planar_rgb_alpha_premultiplied_every_pair_per_channel(gpu, bits):
+    """Planar RGB + premultiplied alpha: alpha = row; R = col, G and B = col shifted by a third and two thirds of the range -- along a
+    row every channel takes every code, so each channel meets every (code, alpha) pair."""
+    code, alpha = xi.pairs(bits)
+    n = 1 << bits
+    shift = lambda k: ((code.astype(np.uint32) + k * (n // 3)) % n).astype(code.dtype)
+    planes = {0: code, 1: shift(1), 2: shift(2), 3: alpha}
+    for pl in (1, 2):
+        assert np.array_equal(np.sort(planes[pl], axis=1), code)
+    d = pkg.ReadDesc(width=n, height=n, colorspace=pkg.COLORSPACE_RGB, chroma=pkg.CHROMA_444, bit_depth=bits, depth=_host_depth(bits),
+                     alpha_state=pkg.ALPHA_PREMULTIPLIED, matrix_coefficients=pkg.MATRIX_RGB_GBR)
+    _open_and_compare(gpu, d, planes, harness.oracle_read(d, planes), pads=(0, ODD_PAD) if bits < 12 else (0,), what=(bits,))
+
+
+@pytest.mark.parametrize("fr", [1, 0], ids=["full", "limited"])
+@pytest.mark.parametrize("chroma", ["444", "422", "420"])
+@pytest.mark.parametrize("bits", [8, 10, 12])
+def test_open_ycbcr_alpha_premultiplied_latin_square(gpu, bits, chroma, fr):
+    """YCbCr + premultiplied alpha on the Latin square, BT.709 (at 8 bit also FCC), both ranges; alpha = (3 row + 5 col + 1) mod n takes every code --
+    0 and opaque among them -- in every row and column.  At 8 bit also straight alpha: the sub-sampled 8-bit opens with alpha are
+    the table-free ones of that host depth."""
+    planes = dict(_latin(bits, chroma))
+    planes[3] = xi.latin_alpha(bits, planes[0].shape)
+    states = (pkg.ALPHA_PREMULTIPLIED, pkg.ALPHA_STRAIGHT) if bits == 8 else (pkg.ALPHA_PREMULTIPLIED,)
+    # 256 x 256 pixels are few: FCC joins at 8 bit, the matrix on which an oracle with one contracted multiply-add shows on this square
+    matrices = (pkg.MATRIX_BT709, pkg.MATRIX_FCC) if bits == 8 else (pkg.MATRIX_BT709,)
+    for a in states:
+        for m in matrices:
+            d = _ycc_desc(planes, chroma, bits, _host_depth(bits), m, fr, alpha=a)
+            _open_and_compare(gpu, d, planes, harness.oracle_read(d, planes), pads=(0, ODD_PAD) if bits < 12 else (0,), what=(bits, chroma, fr, a, m))
+
+
+# ---- IEEE division instead of the three-FMA quotient --------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", ["latin12", "triples8-bt709"])
+def test_open_with_ieee_division(gpu, case):
+    """Tuning bit 128 keeps x / kg an IEEE division whatever the divisor (the route of a kg outside the 15 verified ones).  It must give
+    the oracle's bytes on the same exhaustive inputs as the three-FMA form above: the 12-bit Latin square and all 8-bit triples, BT.709."""
+    variant = DEFAULT_VARIANT | 128
+    if case == "latin12":
+        planes, bits, depth = _latin(12, "444"), 12, 16
+    else:
+        planes, bits, depth = _triples("444", 0), 8, 8
+    try:
+        gpu.lib.avifgpu_set_hot_variant(variant)
+        for fr in (1, 0):
+            d = _ycc_desc(planes, "444", bits, depth, pkg.MATRIX_BT709, fr)
+            _open_and_compare(gpu, d, planes, harness.oracle_read(d, planes), pads=(0,), variant=variant, what=(case, fr))
+    finally:
+        gpu.lib.avifgpu_set_hot_variant(DEFAULT_VARIANT)
+
+
+# ---- the one-off proof behind div_by_kg, rerun on this device --------------------------------------------------------------------------
+def test_three_fma_division_claim_holds_on_this_device():
+    """tools/divcheck: x / kg as three FMAs equals the IEEE quotient for every float x the G equation can divide, for each of the 15
+    divisors the read kernels take that form for -- one `mismatches=0` line per divisor, none of them `NOT usable`.  Built by the
+    package Makefile with hipcc, like the two checkers of tests/test_gpu_read.py::test_unpremultiply_claims_hold_on_this_device; a
+    missing binary is an error here, not a skip.  0.35 s on an MI355X."""
+    exe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "divcheck")
+    assert os.path.exists(exe), "tools/divcheck not built (make -C avif-format_amd)"
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.count("mismatches=0") == 15 and "NOT usable" not in r.stdout, r.stdout + r.stderr
