@@ -892,9 +892,7 @@ void avifgpu_shutdown(void)
         if (cur >= 0) (void)hipSetDevice(cur);
     }
     release_device_caches();
-    release_orient_staging();
-    release_upsample_staging();
-    release_crop_staging();
+    release_open_staging();
 }
 
 int32_t avifgpu_get_yuv_coefficients(int32_t has_nclx, int32_t matrix_coefficients, int32_t color_primaries, float out[3])

@@ -6,21 +6,14 @@
 #include <stdint.h>
 
 #include "../../include/avifgpu.h"
+#include "open_geometry.h"
 #include "upsample_window.h"
 
 namespace avifgpu {
 
-// code -> (transpose, flip x, flip y) of the SOURCE coordinate, as orient_kernels.hip has it:
-//   row-mapped  (codes 1 .. 4)   view(y', x') = src(fy ? H - 1 - y' : y',  fx ? W - 1 - x' : x')
-//   transposing (codes 5 .. 8)   view(y', x') = src(fy ? H - 1 - x' : x',  fx ? W - 1 - y' : y')
-struct CropTurn { bool t, fx, fy; };
-inline CropTurn crop_turn(int code)
-{
-    static const CropTurn k[9] = { { false, false, false }, { false, false, false }, { false, true, false }, { false, true, true }, { false, false, true },
-                                   { true, false, false }, { true, false, true }, { true, true, true }, { true, true, false } };
-    return k[code];
-}
-inline bool crop_code_ok(int code) { return code >= 1 && code <= 8; }
+// the one code table (open_geometry.h) under the names this file and its check program have always used
+using CropTurn = OpenTurn;
+inline CropTurn crop_turn(int code) { return kOpenTurn[code]; }
 
 // a rectangle of a width x height image: 0 <= x0, 1 <= w, x0 + w <= width, and the same in y
 inline bool crop_rect_ok(const avifgpu_rect& r, int width, int height)
@@ -63,12 +56,11 @@ inline bool clap_to_rect(int width, int height, const int32_t clap[8], avifgpu_r
 // ---- a crop given in the coordinates of view = orient(code, F[current]) -> the stored rectangle ----------------------------------------------
 inline void crop_view_size(const avifgpu_rect& r, int code, int& vw, int& vh)
 {
-    const CropTurn o = crop_turn(code);
-    vw = o.t ? r.height : r.width; vh = o.t ? r.width : r.height;
+    open_view_size(r.width, r.height, code, vw, vh);
 }
 inline bool crop_compose(const avifgpu_rect& cur, int code, const avifgpu_rect& v, avifgpu_rect& out)
 {
-    if (!crop_code_ok(code) || cur.x0 < 0 || cur.y0 < 0 || cur.width < 1 || cur.height < 1) return false;
+    if (!open_code_ok(code) || cur.x0 < 0 || cur.y0 < 0 || cur.width < 1 || cur.height < 1) return false;
     if ((int64_t)cur.x0 + cur.width > 0x7fffffffLL || (int64_t)cur.y0 + cur.height > 0x7fffffffLL) return false;
     int vw, vh;
     crop_view_size(cur, code, vw, vh);
@@ -112,19 +104,17 @@ inline CropCover crop_cover(const avifgpu_rect& t, int xs, int ys)
     return k;
 }
 
-inline int64_t crop_align256(int64_t v) { return (v + 255) / 256 * 256; }
-
 // Device scratch for the stored rectangle t (see avifgpu_read_cropped_scratch_bytes): interp = the two upsampled chroma rectangles are
 // needed; s / b = bytes per plane sample / per host pixel.  worst_x / worst_y: count the covering column / row whether t starts odd or not
 // (the helper does not know where a tile will start in the cut direction).
 inline int64_t crop_scratch_bytes(const avifgpu_rect& t, int xs, int ys, bool interp, int code, int s, int b, bool worst_x, bool worst_y)
 {
     if (t.width < 1 || t.height < 1) return 0;
-    if (interp) return 2 * crop_align256((int64_t)t.width * s) * t.height + (code == 1 ? 0 : crop_align256((int64_t)t.width * b) * t.height);
+    if (interp) return 2 * align256((int64_t)t.width * s) * t.height + (code == 1 ? 0 : align256((int64_t)t.width * b) * t.height);
     const int px = (xs && t.width > 1 && (worst_x || (t.x0 & 1))) ? 1 : 0;
     const int py = (ys && t.height > 1 && (worst_y || (t.y0 & 1))) ? 1 : 0;
     if (code == 1 && !px && !py) return 0;
-    return crop_align256((int64_t)(t.width + px) * b) * (t.height + py);
+    return align256((int64_t)(t.width + px) * b) * (t.height + py);
 }
 
 // ---- tiles ---------------------------------------------------------------------------------------------------------------------------------

@@ -7,6 +7,8 @@
 //   * replicated chroma: the existing open on the COVERING rectangle -- T with its start rounded down to even in every subsampled
 //     direction -- from advanced plane pointers; straight into dst where T is its own covering rectangle and the code is 1, otherwise into
 //     scratch, and crop_rows (code 1) or the orient kernels (codes 2-8) move the pixels of T from one pixel and / or one row in.
+// The entry's shared argument checks and the host-pointer path are staged_open.cpp's, which this file gives its cut rule
+// (crop_next_tile), the staged rectangle of a tile and the device path above.
 //
 // crop_rows.  A 2-D byte mover that knows nothing of colour: `rows` rows of `rb` bytes from src (any byte offset into rows of a pitch that
 // is a multiple of 256) to dst (any base, any stride).  A wave owns 1 KiB of a destination row ON THE DESTINATION'S 16-BYTE GRID: chunk k
@@ -73,15 +75,11 @@ hipError_t launch_crop(const uint8_t* src, int64_t src_stride, uint8_t* dst, int
     return hipGetLastError();
 }
 
-bool upsampling_ok(int u) { return u >= AVIFGPU_UPSAMPLE_NEAREST && u <= AVIFGPU_UPSAMPLE_BILINEAR_LEFT; }
-
 // the two chroma planes are interpolated: a bilinear mode on a subsampled YCbCr image
 bool interpolated(const avifgpu_read_desc* d, const ReadGeom& g, int upsampling)
 {
     return upsampling != AVIFGPU_UPSAMPLE_NEAREST && d->colorspace == AVIFGPU_COLORSPACE_YCBCR && g.xs != 0;
 }
-
-bool plane_is_chroma(const avifgpu_read_desc* d, int pl) { return d->colorspace == AVIFGPU_COLORSPACE_YCBCR && (pl == 1 || pl == 2); }
 
 struct Call {
     ReadGeom g;
@@ -93,7 +91,7 @@ struct Call {
 int check_cropped(const avifgpu_read_desc* d, const avifgpu_rect* rect, int upsampling, int code, Call& c, const char* who)
 {
     if (!upsampling_ok(upsampling)) return fail(AVIFGPU_formatBadParameters, "%s: chroma upsampling %d is not an AVIFGPU_UPSAMPLE_* value", who, upsampling);
-    if (!crop_code_ok(code)) return fail(AVIFGPU_formatBadParameters, "%s: orientation %d is not an EXIF code 1..8", who, code);
+    if (!open_code_ok(code)) return fail(AVIFGPU_formatBadParameters, "%s: orientation %d is not an EXIF code 1..8", who, code);
     const int err = check_read(d, 0, 0, c.g);
     if (err) return err;
     if (!rect) return fail(AVIFGPU_formatBadParameters, "%s: null rectangle", who);
@@ -133,7 +131,7 @@ int open_rect_device(const avifgpu_read_desc* d, const Call& c, const avifgpu_re
     int err;
     hipError_t e;
     if (c.interp) {
-        const int64_t up_pitch = crop_align256((int64_t)t.width * c.ssz);
+        const int64_t up_pitch = align256((int64_t)t.width * c.ssz);
         void* const up[2] = { scratch, scratch + up_pitch * t.height };
         const void* const cplanes[2] = { src[1], src[2] };
         const int64_t cstrides[2] = { src_stride[1], src_stride[2] };
@@ -146,7 +144,7 @@ int open_rect_device(const avifgpu_read_desc* d, const Call& c, const avifgpu_re
         const int64_t strides[4] = { src_stride[0], up_pitch, up_pitch, c.g.alpha ? src_stride[3] : 0 };
         if (code == 1) return avifgpu_read_rows(&sub, 0, sub.height, planes, strides, dst, dst_row_bytes, AVIFGPU_MEM_DEVICE, st);
         uint8_t* const img = scratch + 2 * up_pitch * t.height;
-        const int64_t pitch = crop_align256((int64_t)t.width * c.bpp);
+        const int64_t pitch = align256((int64_t)t.width * c.bpp);
         if ((err = avifgpu_read_rows(&sub, 0, sub.height, planes, strides, img, pitch, AVIFGPU_MEM_DEVICE, st))) return err;
         return avifgpu_probe_orient(code, c.bpp, t.width, t.height, img, pitch, dst, dst_row_bytes, st);
     }
@@ -156,7 +154,7 @@ int open_rect_device(const avifgpu_read_desc* d, const Call& c, const avifgpu_re
     sub_image(d, c.g, c.ssz, k.c, src, src_stride, sub, psrc);
     if (code == 1 && !k.px && !k.py)                           // the existing kernels, straight into dst
         return avifgpu_read_rows(&sub, 0, sub.height, psrc, src_stride, dst, dst_row_bytes, AVIFGPU_MEM_DEVICE, st);
-    const int64_t pitch = crop_align256((int64_t)k.c.width * c.bpp);
+    const int64_t pitch = align256((int64_t)k.c.width * c.bpp);
     if ((err = avifgpu_read_rows(&sub, 0, sub.height, psrc, src_stride, scratch, pitch, AVIFGPU_MEM_DEVICE, st))) return err;
     const uint8_t* const from = scratch + (int64_t)k.py * pitch + (int64_t)k.px * c.bpp;
     if (code != 1) return avifgpu_probe_orient(code, c.bpp, t.width, t.height, from, pitch, dst, dst_row_bytes, st);
@@ -167,36 +165,8 @@ int open_rect_device(const avifgpu_read_desc* d, const Call& c, const avifgpu_re
     return 0;
 }
 
-// ---- host path: two staging slots of the library's own on the first bound context ---------------------------------------------------
-struct CropSlot {
-    hipStream_t stream = nullptr;
-    void* buf[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };      // the four planes, scratch, out
-    size_t cap[6] = { 0, 0, 0, 0, 0, 0 };
-};
-CropSlot g_crop_slots[2];
-int g_crop_device = -1;
-
-void free_crop_slots()
-{
-    for (CropSlot& s : g_crop_slots) {
-        for (int i = 0; i < 6; ++i) if (s.buf[i]) (void)hipFree(s.buf[i]);
-        if (s.stream) (void)hipStreamDestroy(s.stream);
-        s = CropSlot();
-    }
-    g_crop_device = -1;
-}
-
-hipError_t grow(void** p, size_t* cap, size_t need)
-{
-    if (need < 256) need = 256;
-    if (*cap >= need) return hipSuccess;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    const size_t want = need + need / 4;
-    const hipError_t e = hipMalloc(p, want);
-    if (e == hipSuccess) *cap = want;
-    return e;
-}
-
+// ---- host path: the staged driver (staged_open.cpp) with the STAGED image of a tile (crop_stage_rect): only its part of each plane goes up,
+// as a strided copy, and the device path treats it as a whole image --------------------------------------------------------------------
 constexpr size_t kHostTileBytes = (size_t)16 << 20;             // output bytes of one staged tile
 
 bool cut_matters(const avifgpu_read_desc* d, const Call& c, int code)
@@ -208,69 +178,33 @@ bool cut_matters(const avifgpu_read_desc* d, const Call& c, int code)
 int read_rows_cropped_host(const avifgpu_read_desc* d, const Call& c, const avifgpu_rect& rect, int upsampling, int code, int orow0, int onrows,
                            const void* const src[4], const int64_t src_stride[4], uint8_t* dst, int64_t dst_row_bytes)
 {
-    HostCallGuard serial;
-    const int device = context_device(0);
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice", AVIFGPU_readErr);
-    if (g_crop_device != device) {
-        if (g_crop_device >= 0) { (void)hipSetDevice(g_crop_device); free_crop_slots(); (void)hipSetDevice(device); }
-        g_crop_device = device;
-    }
-    int err = 0;
     const bool subsampled = d->colorspace == AVIFGPU_COLORSPACE_YCBCR;
     const int xs = subsampled ? c.g.xs : 0, ys = subsampled ? c.g.ys : 0;
     const bool matters = cut_matters(d, c, code);
-    const int max_rows = (int)std::max<int64_t>(2, std::min<int64_t>((int64_t)(kHostTileBytes / (size_t)std::max<int64_t>((int64_t)c.out_w * c.bpp, 1)), 1 << 30));
-    int k = 0;
-    for (int o0 = orow0; o0 < orow0 + onrows && !err; ++k) {
+    const int64_t out_pitch = align256((int64_t)c.out_w * c.bpp);              // every tile's output is c.out_w wide
+    avifgpu_read_desc sd = *d;                                 // the staged image
+    avifgpu_rect tin;                                          // the tile's rectangle inside it
+    const StagedPlan plan = [&](int o0, int left, int max_rows, StagedTile& t) {
         // cut inside the caller's range, on the helper's rule: the range's own end is a cut like any other
-        int n = std::min(crop_next_tile(rect, code, matters, o0, max_rows), orow0 + onrows - o0);
-        const avifgpu_rect t = crop_tile_rect(rect, code, o0, n);
-        const avifgpu_rect sr = crop_stage_rect(t, d->width, d->height, xs, ys, c.interp);
-        CropSlot& s = g_crop_slots[k & 1];
-        if (!s.stream && (e = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking)) != hipSuccess) { err = hip_fail(e, "hipStreamCreate", AVIFGPU_readErr); break; }
-        if ((e = hipStreamSynchronize(s.stream)) != hipSuccess) { err = hip_fail(e, "cropped open: staged tile", AVIFGPU_readErr); break; }
-        // the staged image: only its part of each plane goes up, as a strided copy
-        avifgpu_read_desc sd = *d;
+        t.n = std::min(crop_next_tile(rect, code, matters, o0, max_rows), left);
+        tin = crop_tile_rect(rect, code, o0, t.n);
+        const avifgpu_rect sr = crop_stage_rect(tin, d->width, d->height, xs, ys, c.interp);
         sd.width = sr.width; sd.height = sr.height;
-        const void* dsrc[4] = { nullptr, nullptr, nullptr, nullptr };
-        int64_t dstride[4] = { 0, 0, 0, 0 };
-        for (int pl = 0; pl < 4 && !err; ++pl) {
+        for (int pl = 0; pl < 4; ++pl) {
             if (!read_plane_used(d, c.g, pl) || !src[pl]) continue;
             const avifgpu_rect pr = crop_plane_rect(sr, plane_is_chroma(d, pl), xs, ys);
             const int64_t wbytes = (int64_t)pr.width * c.ssz;
-            dstride[pl] = crop_align256(wbytes);
-            if ((e = grow(&s.buf[pl], &s.cap[pl], (size_t)(dstride[pl] * pr.height))) != hipSuccess) { err = hip_fail(e, "hipMalloc", AVIFGPU_memFullErr); break; }
-            const uint8_t* const h = static_cast<const uint8_t*>(src[pl]) + (int64_t)pr.y0 * src_stride[pl] + (int64_t)pr.x0 * c.ssz;
-            if ((e = hipMemcpy2DAsync(s.buf[pl], (size_t)dstride[pl], h, (size_t)src_stride[pl], (size_t)wbytes, (size_t)pr.height, hipMemcpyHostToDevice, s.stream)) != hipSuccess) {
-                err = hip_fail(e, "hipMemcpy2DAsync (planes)", AVIFGPU_readErr); break;
-            }
-            dsrc[pl] = s.buf[pl];
+            t.up[pl] = { static_cast<const uint8_t*>(src[pl]) + (int64_t)pr.y0 * src_stride[pl] + (int64_t)pr.x0 * c.ssz, src_stride[pl], wbytes, pr.height, align256(wbytes) };
         }
-        if (err) break;
-        avifgpu_rect tin = t;                                  // t inside the staged image
         tin.x0 -= sr.x0; tin.y0 -= sr.y0;
-        int tw, th;
-        crop_view_size(t, code, tw, th);                       // the tile's output: tw x n
-        const int64_t out_pitch = crop_align256((int64_t)tw * c.bpp);
-        if ((e = grow(&s.buf[5], &s.cap[5], (size_t)(out_pitch * n))) != hipSuccess) { err = hip_fail(e, "hipMalloc", AVIFGPU_memFullErr); break; }
-        if ((e = grow(&s.buf[4], &s.cap[4], (size_t)scratch_need(&sd, c, tin, code))) != hipSuccess) { err = hip_fail(e, "hipMalloc", AVIFGPU_memFullErr); break; }
-        if ((err = open_rect_device(&sd, c, tin, upsampling, code, dsrc, dstride, static_cast<uint8_t*>(s.buf[5]), out_pitch, static_cast<uint8_t*>(s.buf[4]), s.stream))) break;
-        if ((e = hipMemcpy2DAsync(dst + (int64_t)(o0 - orow0) * dst_row_bytes, (size_t)dst_row_bytes, s.buf[5], (size_t)out_pitch, (size_t)((int64_t)tw * c.bpp), (size_t)n,
-                                  hipMemcpyDeviceToHost, s.stream)) != hipSuccess) {
-            err = hip_fail(e, "hipMemcpy2DAsync (rows)", AVIFGPU_readErr); break;
-        }
-        o0 += n;
-    }
-    for (CropSlot& s : g_crop_slots) {                         // drained also after a failure: nothing of this call stays in flight
-        if (!s.stream) continue;
-        e = hipStreamSynchronize(s.stream);
-        if (e != hipSuccess && !err) err = hip_fail(e, "cropped open: staged tile", AVIFGPU_readErr);
-    }
-    if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
-    return err;
+        t.out_pitch = out_pitch;
+        t.scratch_bytes = scratch_need(&sd, c, tin, code);
+        return 0;
+    };
+    const StagedEnqueue enqueue = [&](const StagedBuffers& b) {
+        return open_rect_device(&sd, c, tin, upsampling, code, b.plane, b.pitch, static_cast<uint8_t*>(b.out), out_pitch, static_cast<uint8_t*>(b.scratch), b.stream);
+    };
+    return staged_open("cropped open", kHostTileBytes, (int64_t)c.out_w * c.bpp, orow0, onrows, dst, dst_row_bytes, plan, enqueue);
 }
 
 // the call is one the upsampled open serves byte for byte: the whole image, cut where that entry allows
@@ -285,17 +219,6 @@ bool hand_on(const avifgpu_read_desc* d, const Call& c, const avifgpu_rect& rect
 }
 
 } // namespace
-
-void release_crop_staging()
-{
-    HostCallGuard serial;
-    if (g_crop_device < 0) return;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
-    if (hipSetDevice(g_crop_device) == hipSuccess) free_crop_slots();
-    else { (void)hipGetLastError(); g_crop_device = -1; for (CropSlot& s : g_crop_slots) s = CropSlot(); }
-    if (prev >= 0) (void)hipSetDevice(prev);
-}
 
 } // namespace avifgpu
 
@@ -373,21 +296,19 @@ int32_t avifgpu_read_rows_cropped(const avifgpu_read_desc* desc, const avifgpu_r
     if (err) return err;
     if (orow0 < 0 || onrows < 0 || (int64_t)orow0 + onrows > c.out_h)
         return fail(AVIFGPU_formatBadParameters, "avifgpu_read_rows_cropped: rows [%d, %d + %d) outside the %d rows of the cropped image", orow0, orow0, onrows, c.out_h);
-    if (mem_kind != AVIFGPU_MEM_HOST && mem_kind != AVIFGPU_MEM_DEVICE) return fail(AVIFGPU_formatBadParameters, "bad mem_kind %d", mem_kind);
-    if (!src || !src_stride || !dst) return fail(AVIFGPU_formatBadParameters, "null buffer");
-    if ((int64_t)c.out_w * c.bpp > 0x7fffffffLL) return fail(AVIFGPU_memFullErr, "rowBytes exceeds int32");
-    if (dst_row_bytes < (int64_t)c.out_w * c.bpp) return fail(AVIFGPU_formatBadParameters, "dst_row_bytes %lld < %lld", (long long)dst_row_bytes, (long long)c.out_w * c.bpp);
-    // the whole image's planes, as avifgpu_read_rows checks a tile's
-    if ((err = check_read_buffers(desc, c.g, desc->height, src, src_stride, dst, (int64_t)desc->width * c.bpp))) return err;
     const avifgpu_rect t = crop_tile_rect(*rect, orientation, orow0, onrows);
-    if (hand_on(desc, c, *rect, orientation, t, onrows))       // the existing entries, byte for byte; the new code object is not loaded
-        return avifgpu_read_rows_upsampled(desc, upsampling, orientation, orow0, onrows, src, src_stride, dst, dst_row_bytes, scratch, scratch_bytes, mem_kind, stream);
     const int64_t need = scratch_need(desc, c, t, orientation);
-    if (mem_kind == AVIFGPU_MEM_DEVICE && need > 0 && (!scratch || scratch_bytes < need))
-        return fail(AVIFGPU_formatBadParameters, "avifgpu_read_rows_cropped: %lld bytes of scratch, %lld needed (avifgpu_read_cropped_scratch_bytes)", (long long)(scratch ? scratch_bytes : 0), (long long)need);
-    if (c.interp && ((int64_t)t.height + 31) / 32 > 65535) return fail(AVIFGPU_formatBadParameters, "avifgpu_read_rows_cropped: a region of %d rows (cut it)", t.height);
-    if (context_count() == 0) return fail(AVIFGPU_formatBadParameters, "avifgpu_init has not succeeded: no HIP device bound (no CPU fallback)");
-    if (onrows == 0) return 0;
+    const OpenEntry entry = { "avifgpu_read_rows_cropped", "avifgpu_read_cropped_scratch_bytes", desc, &c.g, c.out_w, c.bpp, onrows,
+                              src, src_stride, dst, dst_row_bytes, scratch, scratch_bytes, mem_kind };
+    err = check_open_entry(entry, need, [&](int step) {
+        if (step == 0 && hand_on(desc, c, *rect, orientation, t, onrows)) {      // the existing entries, byte for byte; the new code object is not loaded
+            const int rc = avifgpu_read_rows_upsampled(desc, upsampling, orientation, orow0, onrows, src, src_stride, dst, dst_row_bytes, scratch, scratch_bytes, mem_kind, stream);
+            return rc ? rc : kOpenEntryOver;
+        }
+        if (step == 1 && c.interp && ((int64_t)t.height + 31) / 32 > 65535) return fail(AVIFGPU_formatBadParameters, "avifgpu_read_rows_cropped: a region of %d rows (cut it)", t.height);
+        return 0;
+    });
+    if (err) return err == kOpenEntryOver ? 0 : err;
 
     if (mem_kind == AVIFGPU_MEM_DEVICE)
         return open_rect_device(desc, c, t, upsampling, orientation, src, src_stride, static_cast<uint8_t*>(dst), dst_row_bytes, static_cast<uint8_t*>(scratch), (hipStream_t)stream);

@@ -5,6 +5,8 @@
 // the region's size, plane pointers advanced, the same strides) into scratch; one of the two kernels below then MOVES whole host pixels
 // from scratch to dst.  They know nothing of colour: a pixel is BPP bytes, BPP in {1, 2, 3, 4, 6, 8, 12, 16} (gray / gray+A / RGB / RGBA at
 // 8 / 16 / 32 bit).  A translation unit -- and so a code object -- of its own: a process that never opens an oriented image never loads it.
+// The code table and the region are open_geometry.h's; the entry's shared argument checks and the host-pointer path (tiles through two
+// staging slots) are staged_open.cpp's, which this file gives its cut rule, what goes up for a tile and what is enqueued.
 //
 // Every code is (transpose, flip x, flip y) of the SOURCE coordinate:
 //   row-mapped  (codes 2, 3, 4)   dst(y', x') = src(fy ? R - 1 - y' : y',  fx ? W - 1 - x' : x')
@@ -248,19 +250,10 @@ __global__ __launch_bounds__(kOrientThreads) void orient_transpose(const OrientP
     }
 }
 
-// code -> (transpose, flip x, flip y) of the source coordinate
-struct Orient { bool t, fx, fy; };
-constexpr Orient kOrient[9] = { { false, false, false }, { false, false, false }, { false, true, false }, { false, true, true }, { false, false, true },
-                                { true, false, false }, { true, false, true }, { true, true, true }, { true, true, false } };
-
-bool code_ok(int code) { return code >= 1 && code <= 8; }
-
-int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
-
 hipError_t launch_orient(int code, int bpp, const uint8_t* src, int64_t src_stride, int ws, int hs, uint8_t* dst, int64_t dst_stride, hipStream_t st)
 {
     if (ws <= 0 || hs <= 0) return hipSuccess;
-    const Orient o = kOrient[code];
+    const OpenTurn o = kOpenTurn[code];
     OrientParams p;
     memset(&p, 0, sizeof(p));
     p.src = src; p.src_stride = src_stride; p.dst = dst; p.dst_stride = dst_stride; p.ws = ws; p.hs = hs; p.fx = o.fx; p.fy = o.fy;
@@ -291,41 +284,21 @@ hipError_t launch_orient(int code, int bpp, const uint8_t* src, int64_t src_stri
     return hipGetLastError();
 }
 
-// ---- the source region of output rows [orow0, orow0 + onrows) ----------------------------------------------------------------------
-struct Region {
-    Orient o;
-    int out_w, out_h;        // the oriented image
-    int start;               // first source row (codes 1-4) / column (codes 5-8) of the region
-    int sub_w, sub_h;        // the sub-image the read kernels decode
-    int bpp;
-    bool subsampled;         // the cut direction is subsampled
-};
-
-int region_of(const avifgpu_read_desc* d, const ReadGeom& g, int code, int orow0, int onrows, Region& r)
+// ---- the source region of output rows [orow0, orow0 + onrows): OpenRegion (open_geometry.h) -------------------------------------------
+int oriented_region(const avifgpu_read_desc* d, const ReadGeom& g, int code, int orow0, int onrows, OpenRegion& r)
 {
-    r.o = kOrient[code];
-    r.out_w = r.o.t ? d->height : d->width;
-    r.out_h = r.o.t ? d->width : d->height;
-    r.bpp = g.nch * (d->depth / 8);
-    if (orow0 < 0 || onrows < 0 || (int64_t)orow0 + onrows > r.out_h) return fail(AVIFGPU_formatBadParameters, "oriented rows [%d, %d + %d) outside the %d rows of the image", orow0, orow0, onrows, r.out_h);
-    const bool flipped = r.o.t ? r.o.fx : r.o.fy;
-    r.start = flipped ? r.out_h - orow0 - onrows : orow0;
-    r.sub_w = r.o.t ? onrows : d->width;
-    r.sub_h = r.o.t ? d->height : onrows;
-    r.subsampled = (r.o.t ? g.xs : g.ys) != 0;
-    return 0;
+    if (region_of(d, g, code, orow0, onrows, r)) return 0;
+    return fail(AVIFGPU_formatBadParameters, "oriented rows [%d, %d + %d) outside the %d rows of the image", orow0, orow0, onrows, r.out_h);
 }
 
-// a region of a subsampled direction starts on an even index; a single row / column is its own chroma sample wherever it lies
-bool legal_cut(const Region& r, int onrows) { return !r.subsampled || (r.start & 1) == 0 || onrows <= 1; }
-
-int next_tile(const Region& whole, int orow0, int max_rows)
+// The oriented open's cut rule.  NOT crop_next_tile (crop_geometry.h): behind a caller's own odd start of an unflipped subsampled direction
+// this one answers 1, that one the n that makes the next start even.  Both are public behaviour.
+int next_tile(const OpenRegion& whole, int orow0, int max_rows)
 {
     const int rest = whole.out_h - orow0;
     int n = std::min(max_rows, rest);
     if (!whole.subsampled || n <= 1) return n;
-    const bool flipped = whole.o.t ? whole.o.fx : whole.o.fy;
-    if (flipped) {
+    if (whole.flipped) {
         if ((whole.out_h - orow0 - n) & 1) --n;                 // n == rest starts at 0
         return n;
     }
@@ -334,10 +307,8 @@ int next_tile(const Region& whole, int orow0, int max_rows)
     return n;
 }
 
-bool plane_is_chroma(const avifgpu_read_desc* d, int pl) { return d->colorspace == AVIFGPU_COLORSPACE_YCBCR && (pl == 1 || pl == 2); }
-
 // descriptor and plane pointers of the region's sub-image
-void sub_image(const avifgpu_read_desc* d, const ReadGeom& g, const Region& r, const void* const src[4], const int64_t src_stride[4],
+void sub_image(const avifgpu_read_desc* d, const ReadGeom& g, const OpenRegion& r, const void* const src[4], const int64_t src_stride[4],
                avifgpu_read_desc& sub, const void* out[4])
 {
     sub = *d;
@@ -352,141 +323,51 @@ void sub_image(const avifgpu_read_desc* d, const ReadGeom& g, const Region& r, c
     }
 }
 
-int64_t scratch_pitch(const Region& r) { return align_up((int64_t)r.sub_w * r.bpp, 256); }
+int64_t scratch_pitch(const OpenRegion& r) { return align256((int64_t)r.sub_w * r.bpp); }
 
-// ---- host path: two staging slots of the library's own on the first bound context ---------------------------------------------------
-struct OrientSlot {
-    hipStream_t stream = nullptr;
-    void* plane[4] = { nullptr, nullptr, nullptr, nullptr };
-    size_t plane_cap[4] = { 0, 0, 0, 0 };
-    void* scratch = nullptr; size_t scratch_cap = 0;
-    void* out = nullptr; size_t out_cap = 0;
-};
-OrientSlot g_slots[2];
-int g_slots_device = -1;
-
-void free_slots()
-{
-    for (OrientSlot& s : g_slots) {
-        for (int pl = 0; pl < 4; ++pl) { if (s.plane[pl]) (void)hipFree(s.plane[pl]); s.plane[pl] = nullptr; s.plane_cap[pl] = 0; }
-        if (s.scratch) (void)hipFree(s.scratch);
-        if (s.out) (void)hipFree(s.out);
-        if (s.stream) (void)hipStreamDestroy(s.stream);
-        s = OrientSlot();
-    }
-    g_slots_device = -1;
-}
-
-hipError_t grow(void** p, size_t* cap, size_t need)
-{
-    if (*cap >= need) return hipSuccess;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    const size_t want = need + need / 4;
-    const hipError_t e = hipMalloc(p, want);
-    if (e == hipSuccess) *cap = want;
-    return e;
-}
-
+// ---- host path: the staged driver (staged_open.cpp) with what goes up for a tile -- the region's part of every plane -- and what runs ---
 constexpr size_t kHostTileBytes = (size_t)32 << 20;             // output bytes of one staged tile
 
 int read_rows_oriented_host(const avifgpu_read_desc* d, const ReadGeom& g, int code, int orow0, int onrows,
                             const void* const src[4], const int64_t src_stride[4], uint8_t* dst, int64_t dst_row_bytes)
 {
-    HostCallGuard serial;
-    const int device = context_device(0);
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice", AVIFGPU_readErr);
-    if (g_slots_device != device) {
-        if (g_slots_device >= 0) { (void)hipSetDevice(g_slots_device); free_slots(); (void)hipSetDevice(device); }
-        g_slots_device = device;
-    }
-    int err = 0;
-    Region whole;
+    OpenRegion whole, r;
     region_of(d, g, code, 0, 0, whole);
     const int ssz = d->bit_depth > 8 ? 2 : 1;
-    const int max_rows = (int)std::max<int64_t>(2, std::min<int64_t>((int64_t)(kHostTileBytes / (size_t)std::max<int64_t>((int64_t)whole.out_w * whole.bpp, 1)), 1 << 30));
-    int k = 0;
-    for (int o0 = orow0; o0 < orow0 + onrows && !err; ++k) {
-        int n = next_tile(whole, o0, std::min(max_rows, orow0 + onrows - o0));
-        Region r;
-        if ((err = region_of(d, g, code, o0, n, r))) break;
-        OrientSlot& s = g_slots[k & 1];
-        if (!s.stream && (e = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking)) != hipSuccess) { err = hip_fail(e, "hipStreamCreate", AVIFGPU_readErr); break; }
-        if ((e = hipStreamSynchronize(s.stream)) != hipSuccess) { err = hip_fail(e, "oriented open: staged tile", AVIFGPU_readErr); break; }
-        avifgpu_read_desc sub;
+    avifgpu_read_desc sub;
+    const int64_t out_pitch = align256((int64_t)whole.out_w * whole.bpp);
+    const StagedPlan plan = [&](int o0, int left, int max_rows, StagedTile& t) {
+        t.n = next_tile(whole, o0, std::min(max_rows, left));
+        const int err = oriented_region(d, g, code, o0, t.n, r);
+        if (err) return err;
         const void* hsrc[4];
         sub_image(d, g, r, src, src_stride, sub, hsrc);
-        const void* dsrc[4] = { nullptr, nullptr, nullptr, nullptr };
-        int64_t dstride[4] = { 0, 0, 0, 0 };
-        for (int pl = 0; pl < 4 && !err; ++pl) {
-            if (!hsrc[pl]) continue;
+        for (int pl = 0; pl < 4; ++pl) {
             const bool chroma = plane_is_chroma(d, pl);
             const int64_t wbytes = (int64_t)(chroma ? (sub.width + g.xs) >> g.xs : sub.width) * ssz;
-            const int64_t rows = chroma ? (sub.height + g.ys) >> g.ys : sub.height;
-            dstride[pl] = align_up(wbytes, 256);
-            if ((e = grow(&s.plane[pl], &s.plane_cap[pl], (size_t)(dstride[pl] * rows))) != hipSuccess) { err = hip_fail(e, "hipMalloc", AVIFGPU_memFullErr); break; }
-            if ((e = hipMemcpy2DAsync(s.plane[pl], (size_t)dstride[pl], hsrc[pl], (size_t)src_stride[pl], (size_t)wbytes, (size_t)rows, hipMemcpyHostToDevice, s.stream)) != hipSuccess) {
-                err = hip_fail(e, "hipMemcpy2DAsync (planes)", AVIFGPU_readErr); break;
-            }
-            dsrc[pl] = s.plane[pl];
+            t.up[pl] = { hsrc[pl], src_stride[pl], wbytes, chroma ? (sub.height + g.ys) >> g.ys : sub.height, align256(wbytes) };
         }
-        if (err) break;
-        const int64_t out_pitch = align_up((int64_t)r.out_w * r.bpp, 256);
-        if ((e = grow(&s.out, &s.out_cap, (size_t)(out_pitch * n))) != hipSuccess) { err = hip_fail(e, "hipMalloc", AVIFGPU_memFullErr); break; }
+        t.out_pitch = out_pitch;
+        t.scratch_bytes = scratch_pitch(r) * r.sub_h;
+        return 0;
+    };
+    const StagedEnqueue enqueue = [&](const StagedBuffers& b) {
         const int64_t sp = scratch_pitch(r);
-        if ((e = grow(&s.scratch, &s.scratch_cap, (size_t)(sp * r.sub_h))) != hipSuccess) { err = hip_fail(e, "hipMalloc", AVIFGPU_memFullErr); break; }
-        err = avifgpu_read_rows(&sub, 0, sub.height, dsrc, dstride, s.scratch, sp, AVIFGPU_MEM_DEVICE, s.stream);
-        if (!err && (e = launch_orient(code, r.bpp, static_cast<const uint8_t*>(s.scratch), sp, r.sub_w, r.sub_h, static_cast<uint8_t*>(s.out), out_pitch, s.stream)) != hipSuccess)
-            err = hip_fail(e, "orient kernel launch", AVIFGPU_readErr);
-        if (err) break;
-        if ((e = hipMemcpy2DAsync(dst + (int64_t)(o0 - orow0) * dst_row_bytes, (size_t)dst_row_bytes, s.out, (size_t)out_pitch, (size_t)((int64_t)r.out_w * r.bpp), (size_t)n,
-                                  hipMemcpyDeviceToHost, s.stream)) != hipSuccess) {
-            err = hip_fail(e, "hipMemcpy2DAsync (rows)", AVIFGPU_readErr); break;
-        }
-        o0 += n;
-    }
-    for (OrientSlot& s : g_slots) {                            // drained also after a failure: nothing of this call stays in flight
-        if (!s.stream) continue;
-        e = hipStreamSynchronize(s.stream);
-        if (e != hipSuccess && !err) err = hip_fail(e, "oriented open: staged tile", AVIFGPU_readErr);
-    }
-    if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
-    return err;
-}
-
-// the orientation as a permutation of a 2 x 3 label array (host only): enough to tell the eight codes apart
-void apply_code(int code, const int* in, int w, int h, int* out, int& ow, int& oh)
-{
-    const Orient o = kOrient[code];
-    ow = o.t ? h : w; oh = o.t ? w : h;
-    for (int y = 0; y < oh; ++y)
-        for (int x = 0; x < ow; ++x) {
-            const int sy = o.t ? (o.fy ? h - 1 - x : x) : (o.fy ? h - 1 - y : y);
-            const int sx = o.t ? (o.fx ? w - 1 - y : y) : (o.fx ? w - 1 - x : x);
-            out[y * ow + x] = in[sy * w + sx];
-        }
+        const int err = avifgpu_read_rows(&sub, 0, sub.height, b.plane, b.pitch, b.scratch, sp, AVIFGPU_MEM_DEVICE, b.stream);
+        if (err) return err;
+        const hipError_t e = launch_orient(code, r.bpp, static_cast<const uint8_t*>(b.scratch), sp, r.sub_w, r.sub_h, static_cast<uint8_t*>(b.out), out_pitch, b.stream);
+        return e == hipSuccess ? 0 : hip_fail(e, "orient kernel launch", AVIFGPU_readErr);
+    };
+    return staged_open("oriented open", kHostTileBytes, (int64_t)whole.out_w * whole.bpp, orow0, onrows, dst, dst_row_bytes, plan, enqueue);
 }
 
 int check_oriented(const avifgpu_read_desc* d, int code, ReadGeom& g, const char* who)
 {
-    if (!code_ok(code)) return fail(AVIFGPU_formatBadParameters, "%s: orientation %d is not an EXIF code 1..8", who, code);
+    if (!open_code_ok(code)) return fail(AVIFGPU_formatBadParameters, "%s: orientation %d is not an EXIF code 1..8", who, code);
     return check_read(d, 0, 0, g);
 }
 
 } // namespace
-
-void release_orient_staging()
-{
-    HostCallGuard serial;
-    if (g_slots_device < 0) return;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
-    if (hipSetDevice(g_slots_device) == hipSuccess) free_slots();
-    else { (void)hipGetLastError(); g_slots_device = -1; for (OrientSlot& s : g_slots) s = OrientSlot(); }
-    if (prev >= 0) (void)hipSetDevice(prev);
-}
 
 } // namespace avifgpu
 
@@ -498,7 +379,7 @@ extern "C" {
 int32_t avifgpu_orientation_compose(int32_t first, int32_t then)
 {
     set_error("");
-    if (!code_ok(first) || !code_ok(then)) return fail(AVIFGPU_formatBadParameters, "avifgpu_orientation_compose: %d, %d: not EXIF codes 1..8", first, then);
+    if (!open_code_ok(first) || !open_code_ok(then)) return fail(AVIFGPU_formatBadParameters, "avifgpu_orientation_compose: %d, %d: not EXIF codes 1..8", first, then);
     const int label[6] = { 0, 1, 2, 3, 4, 5 };
     int a[6], b[6], c[6], aw, ah, bw, bh, cw, ch;
     apply_code(first, label, 3, 2, a, aw, ah);
@@ -517,8 +398,7 @@ int32_t avifgpu_read_oriented_geometry(const avifgpu_read_desc* desc, int32_t or
     const int err = check_oriented(desc, orientation, g, "avifgpu_read_oriented_geometry");
     if (err) return err;
     if (!out_w || !out_h) return fail(AVIFGPU_formatBadParameters, "avifgpu_read_oriented_geometry: null argument");
-    *out_w = kOrient[orientation].t ? desc->height : desc->width;
-    *out_h = kOrient[orientation].t ? desc->width : desc->height;
+    open_view_size(desc->width, desc->height, orientation, *out_w, *out_h);
     return 0;
 }
 
@@ -528,7 +408,7 @@ int32_t avifgpu_read_oriented_next_tile(const avifgpu_read_desc* desc, int32_t o
     ReadGeom g;
     const int err = check_oriented(desc, orientation, g, "avifgpu_read_oriented_next_tile");
     if (err) return err;
-    Region whole;
+    OpenRegion whole;
     region_of(desc, g, orientation, 0, 0, whole);
     if (orow0 < 0 || orow0 >= whole.out_h) return fail(AVIFGPU_formatBadParameters, "avifgpu_read_oriented_next_tile: row %d outside the %d rows of the image", orow0, whole.out_h);
     if (max_rows < 1) return fail(AVIFGPU_formatBadParameters, "avifgpu_read_oriented_next_tile: max_rows %d < 1", max_rows);
@@ -541,8 +421,8 @@ int64_t avifgpu_read_oriented_scratch_bytes(const avifgpu_read_desc* desc, int32
     ReadGeom g;
     const int err = check_oriented(desc, orientation, g, "avifgpu_read_oriented_scratch_bytes");
     if (err) return err;
-    Region r;
-    if (region_of(desc, g, orientation, 0, onrows, r)) return AVIFGPU_formatBadParameters;
+    OpenRegion r;
+    if (oriented_region(desc, g, orientation, 0, onrows, r)) return AVIFGPU_formatBadParameters;
     if (orientation == 1) return 0;
     return scratch_pitch(r) * r.sub_h;
 }
@@ -555,24 +435,17 @@ int32_t avifgpu_read_rows_oriented(const avifgpu_read_desc* desc, int32_t orient
     ReadGeom g;
     int err = check_oriented(desc, orientation, g, "avifgpu_read_rows_oriented");
     if (err) return err;
-    Region r;
-    if ((err = region_of(desc, g, orientation, orow0, onrows, r))) return err;
-    if (mem_kind != AVIFGPU_MEM_HOST && mem_kind != AVIFGPU_MEM_DEVICE) return fail(AVIFGPU_formatBadParameters, "bad mem_kind %d", mem_kind);
-    if (!src || !src_stride || !dst) return fail(AVIFGPU_formatBadParameters, "null buffer");
-    if ((int64_t)r.out_w * r.bpp > 0x7fffffffLL) return fail(AVIFGPU_memFullErr, "rowBytes exceeds int32");
-    if (dst_row_bytes < (int64_t)r.out_w * r.bpp) return fail(AVIFGPU_formatBadParameters, "dst_row_bytes %lld < %lld", (long long)dst_row_bytes, (long long)r.out_w * r.bpp);
-    {   // the whole image's planes, as avifgpu_read_rows checks a tile's
-        avifgpu_read_desc whole = *desc;
-        if ((err = check_read_buffers(&whole, g, desc->height, src, src_stride, dst, (int64_t)desc->width * r.bpp))) return err;
-    }
-    if (!legal_cut(r, onrows))
-        return fail(AVIFGPU_formatBadParameters, "avifgpu_read_rows_oriented: output rows [%d, %d) start at odd source %s %d of a subsampled direction (cut with avifgpu_read_oriented_next_tile)",
-                    orow0, orow0 + onrows, r.o.t ? "column" : "row", r.start);
-    const int64_t need = orientation == 1 ? 0 : scratch_pitch(r) * r.sub_h;
-    if (mem_kind == AVIFGPU_MEM_DEVICE && need > 0 && (!scratch || scratch_bytes < need))
-        return fail(AVIFGPU_formatBadParameters, "avifgpu_read_rows_oriented: %lld bytes of scratch, %lld needed (avifgpu_read_oriented_scratch_bytes)", (long long)(scratch ? scratch_bytes : 0), (long long)need);
-    if (context_count() == 0) return fail(AVIFGPU_formatBadParameters, "avifgpu_init has not succeeded: no HIP device bound (no CPU fallback)");
-    if (onrows == 0) return 0;
+    OpenRegion r;
+    if ((err = oriented_region(desc, g, orientation, orow0, onrows, r))) return err;
+    const OpenEntry entry = { "avifgpu_read_rows_oriented", "avifgpu_read_oriented_scratch_bytes", desc, &g, r.out_w, r.bpp, onrows,
+                              src, src_stride, dst, dst_row_bytes, scratch, scratch_bytes, mem_kind };
+    err = check_open_entry(entry, orientation == 1 ? 0 : scratch_pitch(r) * r.sub_h, [&](int step) {
+        if (step == 0 && !legal_cut(r, onrows))
+            return fail(AVIFGPU_formatBadParameters, "avifgpu_read_rows_oriented: output rows [%d, %d) start at odd source %s %d of a subsampled direction (cut with avifgpu_read_oriented_next_tile)",
+                        orow0, orow0 + onrows, r.o.t ? "column" : "row", r.start);
+        return 0;
+    });
+    if (err) return err == kOpenEntryOver ? 0 : err;
 
     if (mem_kind == AVIFGPU_MEM_HOST) {
         if (orientation == 1) {                                // avifgpu_read_rows: the tile loop of every bound context
@@ -600,7 +473,7 @@ int32_t avifgpu_probe_orient(int32_t orientation, int32_t bytes_per_pixel, int32
     for (int b : { 1, 2, 3, 4, 6, 8, 12, 16 }) ok = ok || b == bytes_per_pixel;
     if (!ok) return fail(AVIFGPU_formatBadParameters, "avifgpu_probe_orient: %d bytes per pixel", bytes_per_pixel);
     if (width < 1 || height < 1 || !src || !dst) return fail(AVIFGPU_formatBadParameters, "avifgpu_probe_orient: bad size or null buffer");
-    const int64_t out_w = kOrient[orientation].t ? height : width;
+    const int64_t out_w = kOpenTurn[orientation].t ? height : width;
     if (src_row_bytes < (int64_t)width * bytes_per_pixel || dst_row_bytes < out_w * bytes_per_pixel)
         return fail(AVIFGPU_formatBadParameters, "avifgpu_probe_orient: row bytes too small");
     if (context_count() == 0) return fail(AVIFGPU_formatBadParameters, "avifgpu_init has not succeeded: no HIP device bound (no CPU fallback)");

@@ -1,7 +1,8 @@
-// staging.h -- internal C++ interface between the three host-side translation units of libavifgpu.so:
+// staging.h -- internal C++ interface between the host-side translation units of libavifgpu.so:
 //   avifgpu_api.hip  validation, descriptor -> kernel parameters, per-device table caches, the extern "C" entry points
 //   pipeline.hip     the bound device contexts: one worker thread + N staging slots per context; row-tile scheduler
 //   host_shim.cpp    the FormatRecord tile protocol above them
+//   staged_open.cpp  the entry checks and the staged host path of the oriented, upsampled and cropped opens
 // Nothing here crosses the C-ABI (include/avifgpu.h is the public surface).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -9,8 +10,11 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <functional>
+
 #include "../../include/avifgpu.h"
 #include "kernel_params.h"
+#include "open_geometry.h"
 
 namespace avifgpu {
 
@@ -99,14 +103,37 @@ uint32_t* summary_host_counters();                   // the calling thread's arm
 hipError_t launch_summary(const avifgpu_write_desc* d, const WriteGeom& g, int row0, int nrows, const uint8_t* const planes[4],
                           const int64_t stride[4], uint32_t* counters, hipStream_t st, int twin = 0);   // twin: avifgpu_probe_summary
 
-// ---- orient_kernels.hip: irot / imir orientation of an open (avifgpu_read_rows_oriented) ------------------------------
-void release_orient_staging();                       // the host path's two staging slots (avifgpu_shutdown); nothing to do if never used
-
-// ---- upsample_kernels.hip: bilinear chroma upsampling of a 4:2:x open (avifgpu_read_rows_upsampled) ----------------------------------
-void release_upsample_staging();                     // the host path's two staging slots (avifgpu_shutdown); nothing to do if never used
-
-// ---- crop_kernels.hip: the clean aperture of an open (avifgpu_read_rows_cropped) ------------------------------------------------------
-void release_crop_staging();                         // the host path's two staging slots (avifgpu_shutdown); nothing to do if never used
+// ---- staged_open.cpp: what avifgpu_read_rows_oriented / _upsampled / _cropped (orient_, upsample_, crop_kernels.hip) share on the host ----
+// The region of output rows [orow0, orow0 + onrows) of an oriented image (open_geometry.h), from its descriptor.
+inline bool region_of(const avifgpu_read_desc* d, const ReadGeom& g, int code, int orow0, int onrows, OpenRegion& r)
+{
+    return open_region(d->width, d->height, g.xs, g.ys, g.nch * (d->depth / 8), code, orow0, onrows, r);
+}
+// The checks the three entries share, with their codes and messages, in the order they have always run: mem_kind, null buffers, the int32
+// limit on rowBytes, dst_row_bytes, check_read_buffers on the whole image, own(0), the scratch size against `need`, own(1),
+// context_count(), onrows == 0.  own(step) = the entry's own checks in their place; whatever it returns but 0 ends the call.
+// Returns 0: go on; kOpenEntryOver: the call is over and returns 0; anything else: the call returns it.
+struct OpenEntry {
+    const char* who; const char* scratch_helper;     // the entry, and the helper its scratch message names
+    const avifgpu_read_desc* desc; const ReadGeom* g;
+    int64_t out_w; int bpp; int onrows;              // the output: pixels of a row, bytes of a pixel
+    const void* const* src; const int64_t* src_stride; void* dst; int64_t dst_row_bytes; void* scratch; int64_t scratch_bytes; int mem_kind;
+};
+constexpr int kOpenEntryOver = 1;
+int  check_open_entry(const OpenEntry& a, int64_t need, const std::function<int(int)>& own);
+// The staged path of a host-pointer call: rows [orow0, orow0 + onrows) of row_bytes payload bytes each, in tiles of at most
+// max(2, tile_bytes / row_bytes) rows, through two slots (a stream, four plane buffers, scratch, out) on the first bound context.
+//   plan(o0, left, max_rows, t)   the tile that starts at output row o0 with `left` rows of the call to go: its rows, what goes up, what it needs
+//   enqueue(b)                    the feature's device path on the slot's buffers and stream; a library error code
+// Uploads, the rows' way down to dst, the slot's reuse and the drain of both streams (also after a failure) are the driver's.
+struct StagedUpload { const void* host; int64_t host_stride, row_bytes, rows, pitch; };    // host == nullptr: nothing goes up for this plane
+struct StagedTile { int n; StagedUpload up[4]; int64_t out_pitch, scratch_bytes; };
+struct StagedBuffers { const void* plane[4]; int64_t pitch[4]; void* out; void* scratch; hipStream_t stream; };
+typedef std::function<int(int o0, int left, int max_rows, StagedTile& t)> StagedPlan;
+typedef std::function<int(const StagedBuffers& b)> StagedEnqueue;
+int  staged_open(const char* name, size_t tile_bytes, int64_t row_bytes, int orow0, int onrows, uint8_t* dst, int64_t dst_row_bytes,
+                 const StagedPlan& plan, const StagedEnqueue& enqueue);
+void release_open_staging();                         // the two slots (avifgpu_shutdown); nothing to do if never used
 
 // ---- write_kernels.hip / read_kernels.hip ---------------------------------------------------------------------------
 hipError_t launch_write(const WriteParams& p, int depth, int planes, bool dst16, int output, int xs, int ys,

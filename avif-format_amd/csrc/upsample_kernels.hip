@@ -3,7 +3,8 @@
 // The decode arithmetic is not copied and no existing kernel is touched.  chroma_upsample writes the two full-resolution chroma planes
 // U(Cb), U(Cr) of a source REGION into scratch, and the existing 4:4:4 open (avifgpu_read_rows, behind it the existing orient kernels for
 // codes 2-8) then runs on (Y, U(Cb), U(Cr), A) with a copy of the descriptor.  A translation unit -- and so a code object -- of its own: a
-// process that never asks for interpolation never loads it.
+// process that never asks for interpolation never loads it.  The region is open_geometry.h's; the entry's shared argument checks and the
+// host-pointer path are staged_open.cpp's, which this file tells what goes up for a tile (Y, A, the chroma windows) and what is enqueued.
 //
 // The definition is integer and exact (avifgpu.h): per direction two taps with weights in quarters, indices clamped to the WHOLE plane,
 //     U[y, x] = (sum_a sum_b wy_a wx_b C[jy_a, ix_b] + 8) >> 4        -- ONE rounding of the joint sum.
@@ -162,8 +163,6 @@ __global__ __launch_bounds__(kUpThreads) void chroma_upsample(const UpsamplePara
     }
 }
 
-int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
-
 // Enqueue the upsample of both chroma planes.  win[i] / win_stride[i] / (wx0, wy0): the resident window; it must hold what
 // up_need(cw, ch, ys, x0, y0, w, h) names (upsample_window.h).
 hipError_t launch_upsample(int ssz, int ys, int siting, const uint8_t* const win[2], const int64_t win_stride[2], int wx0, int wy0, int cw, int ch,
@@ -198,25 +197,12 @@ hipError_t launch_upsample(int ssz, int ys, int siting, const uint8_t* const win
     return hipGetLastError();
 }
 
-// ---- the source region of output rows [orow0, orow0 + onrows): the oriented open's rule (orient_kernels.hip) ---------------------------
-struct Turn { bool t, fx, fy; };
-constexpr Turn kTurn[9] = { { false, false, false }, { false, false, false }, { false, true, false }, { false, true, true }, { false, false, true },
-                            { true, false, false }, { true, false, true }, { true, true, true }, { true, true, false } };
-
-struct Plan {
-    Turn o;
-    int out_w, out_h;        // the oriented image
-    int start;               // first source row (codes 1-4) / column (codes 5-8) of the region
-    int sub_w, sub_h;        // the region = the sub-image the 4:4:4 open decodes
-    int x0, y0;              // its origin in the stored image
-    int bpp, ssz;
-    bool subsampled;         // the cut direction is subsampled
+// ---- the source region of output rows [orow0, orow0 + onrows): the oriented open's OpenRegion (open_geometry.h), and what is sized by it ----
+struct Plan : OpenRegion {
+    int ssz;
     int64_t up_pitch;        // bytes of a scratch row of U
     int64_t orient_bytes;    // the oriented 4:4:4 open's own scratch (0 for code 1)
 };
-
-bool upsampling_ok(int u) { return u >= AVIFGPU_UPSAMPLE_NEAREST && u <= AVIFGPU_UPSAMPLE_BILINEAR_LEFT; }
-bool code_ok(int code) { return code >= 1 && code <= 8; }
 
 // the call is one of the existing entry points: nothing to interpolate
 bool degenerate(const avifgpu_read_desc* d, const ReadGeom& g, int upsampling)
@@ -226,22 +212,11 @@ bool degenerate(const avifgpu_read_desc* d, const ReadGeom& g, int upsampling)
 
 int plan_of(const avifgpu_read_desc* d, const ReadGeom& g, int code, int orow0, int onrows, Plan& r)
 {
-    r.o = kTurn[code];
-    r.out_w = r.o.t ? d->height : d->width;
-    r.out_h = r.o.t ? d->width : d->height;
-    r.ssz = d->bit_depth > 8 ? 2 : 1;
-    r.bpp = g.nch * (d->depth / 8);
-    if (orow0 < 0 || onrows < 0 || (int64_t)orow0 + onrows > r.out_h)
+    if (!region_of(d, g, code, orow0, onrows, r))
         return fail(AVIFGPU_formatBadParameters, "upsampled rows [%d, %d + %d) outside the %d rows of the image", orow0, orow0, onrows, r.out_h);
-    const bool flipped = r.o.t ? r.o.fx : r.o.fy;
-    r.start = flipped ? r.out_h - orow0 - onrows : orow0;
-    r.sub_w = r.o.t ? onrows : d->width;
-    r.sub_h = r.o.t ? d->height : onrows;
-    r.x0 = r.o.t ? r.start : 0;
-    r.y0 = r.o.t ? 0 : r.start;
-    r.subsampled = (r.o.t ? g.xs : g.ys) != 0;
-    r.up_pitch = align_up((int64_t)r.sub_w * r.ssz, 256);
-    r.orient_bytes = code == 1 ? 0 : align_up((int64_t)r.sub_w * r.bpp, 256) * r.sub_h;
+    r.ssz = d->bit_depth > 8 ? 2 : 1;
+    r.up_pitch = align256((int64_t)r.sub_w * r.ssz);
+    r.orient_bytes = code == 1 ? 0 : align256((int64_t)r.sub_w * r.bpp) * r.sub_h;
     return 0;
 }
 
@@ -267,124 +242,52 @@ int open_region_device(const avifgpu_read_desc* d, const ReadGeom& g, int upsamp
                                       AVIFGPU_MEM_DEVICE, st);
 }
 
-// ---- host path: two staging slots of the library's own on the first bound context ---------------------------------------------------
-struct UpSlot {
-    hipStream_t stream = nullptr;
-    void* buf[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };      // Y, Cb window, Cr window, A, scratch, out
-    size_t cap[6] = { 0, 0, 0, 0, 0, 0 };
-};
-UpSlot g_up_slots[2];
-int g_up_device = -1;
-
-void free_up_slots()
-{
-    for (UpSlot& s : g_up_slots) {
-        for (int i = 0; i < 6; ++i) if (s.buf[i]) (void)hipFree(s.buf[i]);
-        if (s.stream) (void)hipStreamDestroy(s.stream);
-        s = UpSlot();
-    }
-    g_up_device = -1;
-}
-
-hipError_t grow(void** p, size_t* cap, size_t need)
-{
-    if (*cap >= need) return hipSuccess;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    const size_t want = need + need / 4;
-    const hipError_t e = hipMalloc(p, want);
-    if (e == hipSuccess) *cap = want;
-    return e;
-}
-
+// ---- host path: the staged driver (staged_open.cpp).  Y and A: the region.  Chroma: the window stage_window() names (upsample_window.h),
+// the region's samples plus the halo, in the place of the plane ------------------------------------------------------------------------
 constexpr size_t kHostTileBytes = (size_t)32 << 20;             // output bytes of one staged tile, as the oriented open's
 
 int read_rows_upsampled_host(const avifgpu_read_desc* d, const ReadGeom& g, int upsampling, int code, int orow0, int onrows,
                              const void* const src[4], const int64_t src_stride[4], uint8_t* dst, int64_t dst_row_bytes)
 {
-    HostCallGuard serial;
-    const int device = context_device(0);
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
-    hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice", AVIFGPU_readErr);
-    if (g_up_device != device) {
-        if (g_up_device >= 0) { (void)hipSetDevice(g_up_device); free_up_slots(); (void)hipSetDevice(device); }
-        g_up_device = device;
-    }
-    int err = 0;
-    Plan whole;
+    Plan whole, r;
     plan_of(d, g, code, 0, 0, whole);
     const int cw = (d->width + g.xs) >> g.xs, ch = (d->height + g.ys) >> g.ys;
-    const int max_rows = (int)std::max<int64_t>(2, std::min<int64_t>((int64_t)(kHostTileBytes / (size_t)std::max<int64_t>((int64_t)whole.out_w * whole.bpp, 1)), 1 << 30));
-    int k = 0;
-    for (int o0 = orow0; o0 < orow0 + onrows && !err; ++k) {
-        const int n = avifgpu_read_oriented_next_tile(d, code, o0, std::min(max_rows, orow0 + onrows - o0));
-        if (n <= 0) { err = n < 0 ? n : fail(AVIFGPU_readErr, "upsampled open: empty tile"); break; }
-        Plan r;
-        if ((err = plan_of(d, g, code, o0, n, r))) break;
-        UpSlot& s = g_up_slots[k & 1];
-        if (!s.stream && (e = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking)) != hipSuccess) { err = hip_fail(e, "hipStreamCreate", AVIFGPU_readErr); break; }
-        if ((e = hipStreamSynchronize(s.stream)) != hipSuccess) { err = hip_fail(e, "upsampled open: staged tile", AVIFGPU_readErr); break; }
-        // Y and A: the region.  Chroma: the window stage_window() names (upsample_window.h): the region's samples plus the halo
-        const int64_t full_pitch = align_up((int64_t)r.sub_w * r.ssz, 256);
-        for (int pl = 0; pl < 4 && !err; pl += 3) {
+    const int64_t out_pitch = align256((int64_t)whole.out_w * whole.bpp);
+    UpStage sw;
+    const StagedPlan plan = [&](int o0, int left, int max_rows, StagedTile& t) {
+        t.n = avifgpu_read_oriented_next_tile(d, code, o0, std::min(max_rows, left));
+        if (t.n <= 0) return t.n;                              // 0: the driver's "empty tile"
+        const int err = plan_of(d, g, code, o0, t.n, r);
+        if (err) return err;
+        for (int pl = 0; pl < 4; pl += 3) {
             if (pl == 3 && !g.alpha) continue;
             const uint8_t* const h = static_cast<const uint8_t*>(src[pl]) + (int64_t)r.y0 * src_stride[pl] + (int64_t)r.x0 * r.ssz;
-            if ((e = grow(&s.buf[pl], &s.cap[pl], (size_t)(full_pitch * r.sub_h))) != hipSuccess) { err = hip_fail(e, "hipMalloc", AVIFGPU_memFullErr); break; }
-            if ((e = hipMemcpy2DAsync(s.buf[pl], (size_t)full_pitch, h, (size_t)src_stride[pl], (size_t)((int64_t)r.sub_w * r.ssz), (size_t)r.sub_h, hipMemcpyHostToDevice, s.stream)) != hipSuccess)
-                err = hip_fail(e, "hipMemcpy2DAsync (planes)", AVIFGPU_readErr);
+            t.up[pl] = { h, src_stride[pl], (int64_t)r.sub_w * r.ssz, r.sub_h, r.up_pitch };
         }
-        if (err) break;
-        const UpStage sw = stage_window(cw, ch, g.ys, r.ssz, r.x0, r.y0, r.sub_w, r.sub_h);
-        const int64_t wbytes = sw.row_bytes, wrows = sw.rows, win_pitch = sw.pitch;
-        const uint8_t* win[2]; int64_t win_stride[2] = { win_pitch, win_pitch };
-        for (int i = 0; i < 2 && !err; ++i) {
-            const uint8_t* const h = static_cast<const uint8_t*>(src[1 + i]) + stage_host_offset(sw, src_stride[1 + i], r.ssz);
-            if ((e = grow(&s.buf[1 + i], &s.cap[1 + i], (size_t)(win_pitch * wrows))) != hipSuccess) { err = hip_fail(e, "hipMalloc", AVIFGPU_memFullErr); break; }
-            win[i] = static_cast<const uint8_t*>(s.buf[1 + i]);
-            if ((e = hipMemcpy2DAsync(s.buf[1 + i], (size_t)win_pitch, h, (size_t)src_stride[1 + i], (size_t)wbytes, (size_t)wrows, hipMemcpyHostToDevice, s.stream)) != hipSuccess)
-                err = hip_fail(e, "hipMemcpy2DAsync (chroma window)", AVIFGPU_readErr);
-        }
-        if (err) break;
-        const int64_t out_pitch = align_up((int64_t)r.out_w * r.bpp, 256);
-        if ((e = grow(&s.buf[5], &s.cap[5], (size_t)(out_pitch * n))) != hipSuccess) { err = hip_fail(e, "hipMalloc", AVIFGPU_memFullErr); break; }
-        if ((e = grow(&s.buf[4], &s.cap[4], (size_t)scratch_need(r))) != hipSuccess) { err = hip_fail(e, "hipMalloc", AVIFGPU_memFullErr); break; }
-        if ((err = open_region_device(d, g, upsampling, code, r, n, static_cast<const uint8_t*>(s.buf[0]), full_pitch, static_cast<const uint8_t*>(s.buf[3]), full_pitch,
-                                      win, win_stride, sw.need.lo, sw.need.rlo, s.buf[5], out_pitch, static_cast<uint8_t*>(s.buf[4]), s.stream))) break;
-        if ((e = hipMemcpy2DAsync(dst + (int64_t)(o0 - orow0) * dst_row_bytes, (size_t)dst_row_bytes, s.buf[5], (size_t)out_pitch, (size_t)((int64_t)r.out_w * r.bpp), (size_t)n,
-                                  hipMemcpyDeviceToHost, s.stream)) != hipSuccess) {
-            err = hip_fail(e, "hipMemcpy2DAsync (rows)", AVIFGPU_readErr); break;
-        }
-        o0 += n;
-    }
-    for (UpSlot& s : g_up_slots) {                             // drained also after a failure: nothing of this call stays in flight
-        if (!s.stream) continue;
-        e = hipStreamSynchronize(s.stream);
-        if (e != hipSuccess && !err) err = hip_fail(e, "upsampled open: staged tile", AVIFGPU_readErr);
-    }
-    if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
-    return err;
+        sw = stage_window(cw, ch, g.ys, r.ssz, r.x0, r.y0, r.sub_w, r.sub_h);
+        for (int pl = 1; pl <= 2; ++pl)
+            t.up[pl] = { static_cast<const uint8_t*>(src[pl]) + stage_host_offset(sw, src_stride[pl], r.ssz), src_stride[pl], sw.row_bytes, sw.rows, sw.pitch };
+        t.out_pitch = out_pitch;
+        t.scratch_bytes = scratch_need(r);
+        return 0;
+    };
+    const StagedEnqueue enqueue = [&](const StagedBuffers& b) {
+        const uint8_t* const win[2] = { static_cast<const uint8_t*>(b.plane[1]), static_cast<const uint8_t*>(b.plane[2]) };
+        return open_region_device(d, g, upsampling, code, r, r.o.t ? r.sub_w : r.sub_h, static_cast<const uint8_t*>(b.plane[0]), b.pitch[0],
+                                  static_cast<const uint8_t*>(b.plane[3]), b.pitch[3], win, b.pitch + 1, sw.need.lo, sw.need.rlo,
+                                  b.out, out_pitch, static_cast<uint8_t*>(b.scratch), b.stream);
+    };
+    return staged_open("upsampled open", kHostTileBytes, (int64_t)whole.out_w * whole.bpp, orow0, onrows, dst, dst_row_bytes, plan, enqueue);
 }
 
 int check_upsampled(const avifgpu_read_desc* d, int upsampling, int code, ReadGeom& g, const char* who)
 {
     if (!upsampling_ok(upsampling)) return fail(AVIFGPU_formatBadParameters, "%s: chroma upsampling %d is not an AVIFGPU_UPSAMPLE_* value", who, upsampling);
-    if (!code_ok(code)) return fail(AVIFGPU_formatBadParameters, "%s: orientation %d is not an EXIF code 1..8", who, code);
+    if (!open_code_ok(code)) return fail(AVIFGPU_formatBadParameters, "%s: orientation %d is not an EXIF code 1..8", who, code);
     return check_read(d, 0, 0, g);
 }
 
 } // namespace
-
-void release_upsample_staging()
-{
-    HostCallGuard serial;
-    if (g_up_device < 0) return;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
-    if (hipSetDevice(g_up_device) == hipSuccess) free_up_slots();
-    else { (void)hipGetLastError(); g_up_device = -1; for (UpSlot& s : g_up_slots) s = UpSlot(); }
-    if (prev >= 0) (void)hipSetDevice(prev);
-}
 
 } // namespace avifgpu
 
@@ -417,20 +320,16 @@ int32_t avifgpu_read_rows_upsampled(const avifgpu_read_desc* desc, int32_t upsam
         return avifgpu_read_rows_oriented(desc, orientation, orow0, onrows, src, src_stride, dst, dst_row_bytes, scratch, scratch_bytes, mem_kind, stream);
     Plan r;
     if ((err = plan_of(desc, g, orientation, orow0, onrows, r))) return err;
-    if (mem_kind != AVIFGPU_MEM_HOST && mem_kind != AVIFGPU_MEM_DEVICE) return fail(AVIFGPU_formatBadParameters, "bad mem_kind %d", mem_kind);
-    if (!src || !src_stride || !dst) return fail(AVIFGPU_formatBadParameters, "null buffer");
-    if ((int64_t)r.out_w * r.bpp > 0x7fffffffLL) return fail(AVIFGPU_memFullErr, "rowBytes exceeds int32");
-    if (dst_row_bytes < (int64_t)r.out_w * r.bpp) return fail(AVIFGPU_formatBadParameters, "dst_row_bytes %lld < %lld", (long long)dst_row_bytes, (long long)r.out_w * r.bpp);
-    if ((err = check_read_buffers(desc, g, desc->height, src, src_stride, dst, (int64_t)desc->width * r.bpp))) return err;
-    if (r.subsampled && (r.start & 1) != 0 && onrows > 1)
-        return fail(AVIFGPU_formatBadParameters, "avifgpu_read_rows_upsampled: output rows [%d, %d) start at odd source %s %d of a subsampled direction (cut with avifgpu_read_oriented_next_tile)",
-                    orow0, orow0 + onrows, r.o.t ? "column" : "row", r.start);
-    const int64_t need = scratch_need(r);
-    if (mem_kind == AVIFGPU_MEM_DEVICE && need > 0 && (!scratch || scratch_bytes < need))
-        return fail(AVIFGPU_formatBadParameters, "avifgpu_read_rows_upsampled: %lld bytes of scratch, %lld needed (avifgpu_read_upsampled_scratch_bytes)", (long long)(scratch ? scratch_bytes : 0), (long long)need);
-    if (((int64_t)r.sub_h + kUpBand - 1) / kUpBand > 65535) return fail(AVIFGPU_formatBadParameters, "avifgpu_read_rows_upsampled: a region of %d rows (cut it)", r.sub_h);
-    if (context_count() == 0) return fail(AVIFGPU_formatBadParameters, "avifgpu_init has not succeeded: no HIP device bound (no CPU fallback)");
-    if (onrows == 0) return 0;
+    const OpenEntry entry = { "avifgpu_read_rows_upsampled", "avifgpu_read_upsampled_scratch_bytes", desc, &g, r.out_w, r.bpp, onrows,
+                              src, src_stride, dst, dst_row_bytes, scratch, scratch_bytes, mem_kind };
+    err = check_open_entry(entry, scratch_need(r), [&](int step) {
+        if (step == 0 && !legal_cut(r, onrows))
+            return fail(AVIFGPU_formatBadParameters, "avifgpu_read_rows_upsampled: output rows [%d, %d) start at odd source %s %d of a subsampled direction (cut with avifgpu_read_oriented_next_tile)",
+                        orow0, orow0 + onrows, r.o.t ? "column" : "row", r.start);
+        if (step == 1 && ((int64_t)r.sub_h + kUpBand - 1) / kUpBand > 65535) return fail(AVIFGPU_formatBadParameters, "avifgpu_read_rows_upsampled: a region of %d rows (cut it)", r.sub_h);
+        return 0;
+    });
+    if (err) return err == kOpenEntryOver ? 0 : err;
 
     if (mem_kind == AVIFGPU_MEM_HOST)
         return read_rows_upsampled_host(desc, g, upsampling, orientation, orow0, onrows, src, src_stride, static_cast<uint8_t*>(dst), dst_row_bytes);
