@@ -29,9 +29,6 @@ namespace {
 thread_local char g_err[512] = "";
 thread_local char g_kernel[kLabelBytes] = "";
 int g_hot_variant = kHotDefault;
-// the calling thread's code histogram (avifgpu_histogram_attach): host-only bookkeeping, survives a re-binding of the devices
-thread_local uint64_t* g_hist_bins = nullptr;
-thread_local int g_hist_bits = 0, g_hist_kind = AVIFGPU_MEM_HOST;
 }
 
 namespace avifgpu {
@@ -53,24 +50,6 @@ void set_error(const char* msg) { snprintf(g_err, sizeof(g_err), "%s", msg); }
 const char* last_error() { return g_err; }
 void set_last_kernel(const char* label) { snprintf(g_kernel, sizeof(g_kernel), "%s", label); }
 int hot_variant() { return g_hot_variant; }
-
-int histogram_for_call(const avifgpu_write_desc* d, int mem_kind, uint64_t** bins)
-{
-    *bins = nullptr;
-    if (!g_hist_bins || d->depth != 32) return 0;
-    if (d->bit_depth != g_hist_bits)
-        return fail(AVIFGPU_formatBadParameters, "the armed code histogram has %d-bit bins, this call writes %d-bit codes", g_hist_bits, d->bit_depth);
-    if (mem_kind != g_hist_kind)
-        return fail(AVIFGPU_formatBadParameters, "the armed code histogram lives in %s memory, this call's pointers do not",
-                    g_hist_kind == AVIFGPU_MEM_DEVICE ? "device" : "host");
-    *bins = g_hist_bins;
-    return 0;
-}
-uint64_t* histogram_host_bins(int* nbins)
-{
-    *nbins = g_hist_bins ? 1 << g_hist_bits : 0;
-    return g_hist_kind == AVIFGPU_MEM_HOST ? g_hist_bins : nullptr;
-}
 
 } // namespace avifgpu
 
@@ -798,12 +777,8 @@ int write_rows_any(const avifgpu_write_desc* d, const IccArgs& icc, int32_t row0
     if (err) return err;
     if ((err = check_write_buffers(d, g, nrows, src, src_row_bytes, dst, dst_stride))) return err;
     if (context_count() == 0) return fail(AVIFGPU_formatBadParameters, "%s", kNoDevice);
-    uint64_t* hist = nullptr;
-    if ((err = histogram_for_call(d, mem_kind, &hist))) return err;            // before anything is launched
-    ThumbArm thumb;
-    if ((err = thumbnail_for_call(d, g, mem_kind, &thumb))) return err;        // likewise
-    uint32_t* summary = nullptr;
-    if ((err = summary_for_call(mem_kind, &summary))) return err;              // likewise
+    SaveStats stats;                               // the calling thread's armed statistics: a mismatch fails here, before anything is launched
+    if ((err = save_stats_for_call(d, g, mem_kind, &stats))) return err;
     if (nrows == 0) return 0;
     if (icc.c16 || icc.s32 || icc.c8t) icc_epoch_for_call(row0, nrows);       // the device copies of these tables are re-verified once per device and epoch
 
@@ -816,19 +791,7 @@ int write_rows_any(const avifgpu_write_desc* d, const IccArgs& icc, int32_t row0
         for (int pl = 0; pl < 4; ++pl) { p.dst[pl] = (uint8_t*)dst[pl]; p.dst_stride[pl] = dst_stride[pl]; }
         const hipError_t e = launch_write(p, d->depth, d->planes, g.dst16, d->output, g.xs, g.ys, g_hot_variant, st, g_kernel);
         if (e != hipSuccess) return hip_fail(e, "kernel launch", AVIFGPU_writErr);
-        if (hist) {                                     // the statistics kernel behind it on the caller's stream, straight into the caller's device bins
-            const hipError_t eh = launch_write_hist(p, d->planes, reinterpret_cast<unsigned long long*>(hist), st);
-            if (eh != hipSuccess) return hip_fail(eh, "histogram kernel launch", AVIFGPU_writErr);
-        }
-        if (thumb.sums) {                               // the planes just written, summed behind it on the caller's stream into the caller's device sums
-            const hipError_t et = launch_thumbnail(d, g, row0, nrows, p.dst, p.dst_stride, thumb.tw, thumb.th, reinterpret_cast<unsigned long long*>(thumb.sums), st);
-            if (et != hipSuccess) return hip_fail(et, "thumbnail kernel launch", AVIFGPU_writErr);
-        }
-        if (summary) {                                  // the same planes, their extremes raised behind it in the caller's device counters
-            const hipError_t es = launch_summary(d, g, row0, nrows, p.dst, p.dst_stride, summary, st);
-            if (es != hipSuccess) return hip_fail(es, "summary kernel launch", AVIFGPU_writErr);
-        }
-        return 0;
+        return launch_save_stats(d, g, row0, nrows, p, stats, st);   // behind it on the caller's stream, straight into the caller's device targets
     }
     if (mem_kind != AVIFGPU_MEM_HOST) return fail(AVIFGPU_formatBadParameters, "bad mem_kind %d", mem_kind);
     return write_rows_host(d, row0, nrows, src, src_row_bytes, dst, dst_stride, icc);
@@ -955,18 +918,6 @@ int64_t avifgpu_read_algorithmic_bytes(const avifgpu_read_desc* d, int32_t nrows
         total += rows * rb;
     }
     return total;
-}
-
-int32_t avifgpu_histogram_attach(uint64_t* bins, int32_t bit_depth, int32_t mem_kind)
-{
-    g_err[0] = 0;
-    if (!bins) { g_hist_bins = nullptr; g_hist_bits = 0; g_hist_kind = AVIFGPU_MEM_HOST; return 0; }
-    if (bit_depth != 10 && bit_depth != 12)
-        return fail(AVIFGPU_formatBadParameters, "avifgpu_histogram_attach: bit depth %d (a 32-bit document is saved at 10 or 12 bit)", bit_depth);
-    if (mem_kind != AVIFGPU_MEM_HOST && mem_kind != AVIFGPU_MEM_DEVICE)
-        return fail(AVIFGPU_formatBadParameters, "avifgpu_histogram_attach: bad mem_kind %d", mem_kind);
-    g_hist_bins = bins; g_hist_bits = bit_depth; g_hist_kind = mem_kind;
-    return 0;
 }
 
 // SMPTE ST 2084 EOTF, exact rational constants, double: code value in [0, 1] -> cd/m2

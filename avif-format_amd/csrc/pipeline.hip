@@ -61,9 +61,7 @@ struct Job {
     const void* planes_in[4] = {};   int64_t planes_in_stride[4] = {}; // read
     void* rows_out = nullptr;        int64_t rows_out_stride = 0;
     IccArgs icc;
-    bool hist = false;                                     // write, depth 32: the calling thread had a code histogram armed (enqueue side decides, the worker counts)
-    int thumb_tw = 0, thumb_th = 0;                        // write: the calling thread had a thumbnail of this size armed (0: none)
-    bool summary = false;                                  // write: the calling thread had a summary armed (avifgpu_summary_attach)
+    SaveStats stats;                                       // write: what the calling thread had armed (the enqueue side decides, the worker counts into its context's accumulators)
     // filled by start(): what finish() still has to copy out of the pinned bounce buffer
     struct Bounce { uint8_t* dst; int64_t dst_stride; size_t off, pitch, bytes; int rows; } bounce[4];
     int nbounce = 0;
@@ -81,6 +79,45 @@ struct Slot {
     void* h_rows = nullptr;   size_t h_rows_cap = 0;      // pinned: the shim's tile buffer / bounce of pageable rows
     void* h_planes = nullptr; size_t h_planes_cap = 0;    // pinned: bounce of pageable planes
     bool busy = false;                                    // queued or in flight (guarded by Ctx::mu)
+};
+
+// One statistic of the tiles a context converted for an armed caller (save_stats.cpp), accumulated on the context's device: the slots'
+// kernels add into it, wait_all() merges it into the caller's host target and zeroes it again.  Allocated by the worker on first use, freed
+// when it exits.  Plain fields, no atomics: the worker writes them while it starts a tile, before it releases the tile's slot under
+// Ctx::mu (release_slot; a tile that fails goes through record_error and release_slot too); wait_all() reads and clears them after it has
+// seen, under the same mutex, an empty queue and every slot idle; and the next tile reaches the worker through the queue under that mutex.
+struct DeviceAccum {
+    uint8_t* p = nullptr;
+    size_t cap = 0, lo = 0, hi = 0;                        // bytes; [lo, hi): what has been added to since the last drain (empty: clean)
+    // At least `bytes`, zeroed.  Growing frees the old buffer: only on the first armed tile of a call, when nothing of the call is in flight.
+    int ensure(size_t bytes, hipStream_t st, const char* what)
+    {
+        if (bytes <= cap) return 0;
+        release();
+        void* b = nullptr;
+        hipError_t e = hipMalloc(&b, bytes);
+        if (e == hipSuccess) e = hipMemsetAsync(b, 0, bytes, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);     // once: the other slots' streams add into it too
+        if (e != hipSuccess) { if (b) (void)hipFree(b); (void)hipStreamSynchronize(st); return hip_fail(e, what, AVIFGPU_memFullErr); }
+        p = static_cast<uint8_t*>(b); cap = bytes;
+        return 0;
+    }
+    void touch(size_t a, size_t b)
+    {
+        if (b <= a) return;
+        if (hi <= lo) { lo = a; hi = b; } else { lo = std::min(lo, a); hi = std::max(hi, b); }
+    }
+    // What was added since the last drain, into out[0, hi - lo); zeroed again on the device (on the current device's null stream).
+    hipError_t drain(std::vector<uint8_t>& out)
+    {
+        out.resize(hi - lo);
+        hipError_t e = hipMemcpy(out.data(), p + lo, hi - lo, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemsetAsync(p + lo, 0, hi - lo, nullptr);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);    // the slots' streams do not wait for the default stream
+        if (e == hipSuccess) lo = hi = 0;
+        return e;
+    }
+    void release() { if (p) (void)hipFree(p); *this = DeviceAccum(); }
 };
 
 struct Ctx {
@@ -102,23 +139,12 @@ struct Ctx {
     // what this context moved over its device's link since the binding (or the last avifgpu_device_traffic_reset): payload bytes of the
     // tiles it issued, per direction, and how many of them went through a bounce buffer (pageable caller memory)
     std::atomic<uint64_t> tiles{0}, bytes_h2d{0}, bytes_d2h{0}, bytes_bounced{0};
-    // code histogram of the tiles this context converted for an armed caller (avifgpu_histogram_attach): kHistBins 64-bit counters on the
-    // device, allocated and zeroed by the worker on first use, freed when it exits; wait_all() adds them to the caller's bins and zeroes them
-    unsigned long long* d_hist = nullptr;
-    std::atomic<bool> hist_dirty{false};
-    // thumbnail sums of the tiles this context converted for an armed caller (avifgpu_thumbnail_attach): [(ty * tw + tx) * C + c] on the
-    // device, grown and zeroed by the worker; wait_all() adds thumbnail rows [thumb_lo, thumb_hi) -- the only ones touched since it last
-    // ran -- to the caller's sums and zeroes them.  Written by the worker only, read by wait_all() when the context is idle (Ctx::mu orders them).
-    unsigned long long* d_thumb = nullptr;
-    size_t d_thumb_cap = 0;                                // counters
-    int thumb_tw = 0, thumb_th = 0, thumb_c = 0, thumb_lo = 0, thumb_hi = 0;
-    // summary counters of the tiles this context converted for an armed caller (avifgpu_summary_attach): AVIFGPU_SUMMARY_COUNTERS running
-    // maxima on the device, allocated and zeroed by the worker on first use, freed when it exits; wait_all() max-merges them into the
-    // caller's counters and zeroes them
-    uint32_t* d_summary = nullptr;
-    std::atomic<bool> summary_dirty{false};
+    // the statistics of its tiles: kHistBins 64-bit bins (touched as a whole); 64-bit sums [(ty * tw + tx) * C + c] of the thumbnail last
+    // summed for, thumb_tw x thumb_th (touched by the thumbnail rows of each tile: only they travel back); AVIFGPU_SUMMARY_COUNTERS 32-bit maxima
+    DeviceAccum hist, thumb, summary;
+    int thumb_tw = 0, thumb_th = 0;
 };
-constexpr int kHistBins = 4096;
+constexpr size_t kHistBytes = 4096 * sizeof(uint64_t), kSummaryBytes = AVIFGPU_SUMMARY_COUNTERS * sizeof(uint32_t);
 
 // Where a bound device sits in the host: PCI bus id, NUMA node, the node's CPUs ("report which GPUs hang off which
 // root complex").  Read once per binding from sysfs; AVIFGPU_SYSFS_ROOT redirects the reads (tests use a fake tree).
@@ -523,55 +549,31 @@ int start_write(Ctx& c, Job& j)
         c.bytes_d2h.fetch_add((uint64_t)pbytes[pl] * (uint64_t)prow[pl], std::memory_order_relaxed);
         if (!pinned_dst[pl]) c.bytes_bounced.fetch_add((uint64_t)pbytes[pl] * (uint64_t)prow[pl], std::memory_order_relaxed);
     }
-    if (j.hist) {
-        // the statistics kernel on the tile that is already resident (no second upload), on the slot's stream BEHIND the planes' copies back: it
-        // reads d_in only, so the planes leave as early as they do unarmed (the slot is held until the event behind it either way)
-        if (!c.d_hist) {
-            void* hb = nullptr;
-            e = hipMalloc(&hb, kHistBins * sizeof(unsigned long long));
-            if (e == hipSuccess) e = hipMemsetAsync(hb, 0, kHistBins * sizeof(unsigned long long), st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);          // once per context: the other slots' streams count into it too
-            if (e != hipSuccess) { if (hb) (void)hipFree(hb); (void)hipStreamSynchronize(st); return hip_fail(e, "hipMalloc(histogram)", AVIFGPU_memFullErr); }
-            c.d_hist = static_cast<unsigned long long*>(hb);
+    if (j.stats.any()) {
+        // the statistics kernels on the tile that is already resident (no second upload), on the slot's stream BEHIND the planes' copies back:
+        // they only read d_in and d_out, as those copies do, so the planes leave as early as they do unarmed (the slot is held until the event
+        // behind it either way).  The same arms, aimed at this context's accumulators.
+        SaveStats dev = j.stats;
+        if (dev.hist) {
+            if ((err = c.hist.ensure(kHistBytes, st, "hipMalloc(histogram)"))) return err;
+            c.hist.touch(0, kHistBytes);
+            dev.hist = reinterpret_cast<uint64_t*>(c.hist.p);
         }
-        c.hist_dirty.store(true, std::memory_order_release);
-        e = launch_write_hist(p, d->planes, c.d_hist, st);
-        if (e != hipSuccess) { (void)hipStreamSynchronize(st); return hip_fail(e, "histogram kernel launch", AVIFGPU_writErr); }
-    }
-    if (j.thumb_tw > 0) {
-        // the thumbnail sums of the planes that lie in d_out, likewise behind their copies back (which only read d_out, as this does)
-        const size_t need = (size_t)j.thumb_tw * (size_t)j.thumb_th * (size_t)d->planes;
-        if (need > c.d_thumb_cap) {                        // first armed tile, or a larger thumbnail than before: nothing of this call is in flight yet
-            if (c.d_thumb) { (void)hipFree(c.d_thumb); c.d_thumb = nullptr; c.d_thumb_cap = 0; }
-            void* tb = nullptr;
-            e = hipMalloc(&tb, need * sizeof(unsigned long long));
-            if (e == hipSuccess) e = hipMemsetAsync(tb, 0, need * sizeof(unsigned long long), st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);          // the other slots' streams add into it too
-            if (e != hipSuccess) { if (tb) (void)hipFree(tb); (void)hipStreamSynchronize(st); return hip_fail(e, "hipMalloc(thumbnail sums)", AVIFGPU_memFullErr); }
-            c.d_thumb = static_cast<unsigned long long*>(tb); c.d_thumb_cap = need;
-            c.thumb_lo = c.thumb_hi = 0;
+        if (dev.thumb) {
+            const size_t row = (size_t)dev.tw * (size_t)d->planes * sizeof(uint64_t);
+            if ((err = c.thumb.ensure(row * (size_t)dev.th, st, "hipMalloc(thumbnail sums)"))) return err;
+            int lo, hi;
+            thumbnail_rows_of_tile(d, g, j.row0, j.nrows, dev.th, lo, hi);
+            c.thumb.touch((size_t)lo * row, (size_t)hi * row);
+            c.thumb_tw = dev.tw; c.thumb_th = dev.th;
+            dev.thumb = reinterpret_cast<uint64_t*>(c.thumb.p);
         }
-        int lo, hi;
-        thumbnail_rows_of_tile(d, g, j.row0, j.nrows, j.thumb_th, lo, hi);
-        if (c.thumb_hi <= c.thumb_lo) { c.thumb_lo = lo; c.thumb_hi = hi; }
-        else { c.thumb_lo = std::min(c.thumb_lo, lo); c.thumb_hi = std::max(c.thumb_hi, hi); }
-        c.thumb_tw = j.thumb_tw; c.thumb_th = j.thumb_th; c.thumb_c = d->planes;
-        e = launch_thumbnail(d, g, j.row0, j.nrows, p.dst, p.dst_stride, j.thumb_tw, j.thumb_th, c.d_thumb, st);
-        if (e != hipSuccess) { (void)hipStreamSynchronize(st); return hip_fail(e, "thumbnail kernel launch", AVIFGPU_writErr); }
-    }
-    if (j.summary) {
-        // the extremes of the planes that lie in d_out, likewise
-        if (!c.d_summary) {
-            void* sb = nullptr;
-            e = hipMalloc(&sb, AVIFGPU_SUMMARY_COUNTERS * sizeof(uint32_t));
-            if (e == hipSuccess) e = hipMemsetAsync(sb, 0, AVIFGPU_SUMMARY_COUNTERS * sizeof(uint32_t), st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);          // once per context: the other slots' streams raise them too
-            if (e != hipSuccess) { if (sb) (void)hipFree(sb); (void)hipStreamSynchronize(st); return hip_fail(e, "hipMalloc(summary counters)", AVIFGPU_memFullErr); }
-            c.d_summary = static_cast<uint32_t*>(sb);
+        if (dev.summary) {
+            if ((err = c.summary.ensure(kSummaryBytes, st, "hipMalloc(summary counters)"))) return err;
+            c.summary.touch(0, kSummaryBytes);
+            dev.summary = reinterpret_cast<uint32_t*>(c.summary.p);
         }
-        c.summary_dirty.store(true, std::memory_order_release);
-        e = launch_summary(d, g, j.row0, j.nrows, p.dst, p.dst_stride, c.d_summary, st);
-        if (e != hipSuccess) { (void)hipStreamSynchronize(st); return hip_fail(e, "summary kernel launch", AVIFGPU_writErr); }
+        if ((err = launch_save_stats(d, g, j.row0, j.nrows, p, dev, st))) { (void)hipStreamSynchronize(st); return err; }
     }
     if ((e = hipEventRecord(sl.done, st)) != hipSuccess) { (void)hipStreamSynchronize(st); return hip_fail(e, "event record", AVIFGPU_writErr); }
     return 0;
@@ -775,9 +777,7 @@ void worker_main(Ctx* cp)
         if (sl.stream) (void)hipStreamDestroy(sl.stream);
         sl = Slot();
     }
-    if (c.d_hist) { (void)hipFree(c.d_hist); c.d_hist = nullptr; }
-    if (c.d_thumb) { (void)hipFree(c.d_thumb); c.d_thumb = nullptr; c.d_thumb_cap = 0; c.thumb_lo = c.thumb_hi = 0; }
-    if (c.d_summary) { (void)hipFree(c.d_summary); c.d_summary = nullptr; }
+    for (DeviceAccum* a : { &c.hist, &c.thumb, &c.summary }) a->release();
 }
 
 Ctx* ctx_at(int i)
@@ -1022,15 +1022,7 @@ int write_tile_enqueue(int ctx, int slot, const avifgpu_write_desc* d, int row0,
     j.rows_in = src; j.rows_in_stride = src_row_bytes;
     for (int pl = 0; pl < 4; ++pl) { j.planes_out[pl] = dst[pl]; j.planes_out_stride[pl] = dst_stride[pl]; }
     j.icc = icc;
-    uint64_t* hist = nullptr;                              // the arming is the calling thread's; a mismatch fails here, before anything is queued
-    if ((err = histogram_for_call(d, AVIFGPU_MEM_HOST, &hist))) return err;
-    j.hist = hist != nullptr;
-    ThumbArm thumb;                                        // likewise
-    if ((err = thumbnail_for_call(d, g, AVIFGPU_MEM_HOST, &thumb))) return err;
-    if (thumb.sums) { j.thumb_tw = thumb.tw; j.thumb_th = thumb.th; }
-    uint32_t* summary = nullptr;                           // likewise
-    if ((err = summary_for_call(AVIFGPU_MEM_HOST, &summary))) return err;
-    j.summary = summary != nullptr;
+    if ((err = save_stats_for_call(d, g, AVIFGPU_MEM_HOST, &j.stats))) return err;   // the arming is the calling thread's; a mismatch fails here, before anything is queued
     return enqueue(ctx, j);
 }
 
@@ -1061,73 +1053,36 @@ int wait_slot(int ctx, int slot)
 }
 
 namespace {
-// The contexts are idle: add what their tiles counted to the calling thread's armed bins (discard: only zero them), device by device on
-// the calling thread.  The caller's current device is put back.
-int collect_histograms(bool discard)
+// The contexts are idle: merge what their tiles added to their accumulators into the calling thread's HOST arms (discard: only zero it),
+// statistic by statistic, device by device, on the calling thread.  Each statistic merges by its own rule, and only into a target of the
+// size it was accumulated for.  The caller's current device is put back.  Returns the first read-back error in the order histogram,
+// thumbnail, summary.
+int collect(bool discard)
 {
-    uint64_t* bins = nullptr;
+    static const char* const kWhat[3] = { "histogram read-back", "thumbnail read-back", "summary read-back" };
     int nbins = 0;
-    if (!discard) bins = histogram_host_bins(&nbins);
+    const SaveStats to = discard ? SaveStats() : save_stats_host(&nbins);
     int cur = -1, rc = 0;
-    std::vector<unsigned long long> tmp;
-    for (int i = 0; i < context_count(); ++i) {
-        Ctx* c = ctx_at(i);
-        if (!c->d_hist || !c->hist_dirty.load(std::memory_order_acquire)) continue;
-        if (cur == -1 && hipGetDevice(&cur) != hipSuccess) { (void)hipGetLastError(); cur = -2; }
-        tmp.resize(kHistBins);
-        hipError_t e = hipSetDevice(c->device);
-        if (e == hipSuccess) e = hipMemcpy(tmp.data(), c->d_hist, kHistBins * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemsetAsync(c->d_hist, 0, kHistBins * sizeof(unsigned long long), nullptr);
-        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);        // the slots' streams do not wait for the default stream
-        if (e != hipSuccess) { if (!rc) rc = hip_fail(e, "histogram read-back", AVIFGPU_writErr); continue; }
-        c->hist_dirty.store(false, std::memory_order_release);
-        if (bins) for (int k = 0; k < nbins; ++k) bins[k] += tmp[k];
-    }
-    if (cur >= 0) (void)hipSetDevice(cur);
-    return rc;
-}
-// Likewise for the thumbnail sums: only the thumbnail rows the contexts' tiles touched are read back and zeroed.  They are added to the
-// calling thread's armed HOST sums when those still have the size the tiles were summed for.
-int collect_thumbnails(bool discard)
-{
-    int tw = 0, th = 0;
-    uint64_t* sums = discard ? nullptr : thumbnail_host_sums(&tw, &th);
-    int cur = -1, rc = 0;
-    std::vector<unsigned long long> tmp;
-    for (int i = 0; i < context_count(); ++i) {
-        Ctx* c = ctx_at(i);
-        if (!c->d_thumb || c->thumb_hi <= c->thumb_lo) continue;
-        if (cur == -1 && hipGetDevice(&cur) != hipSuccess) { (void)hipGetLastError(); cur = -2; }
-        const size_t row = (size_t)c->thumb_tw * (size_t)c->thumb_c, first = (size_t)c->thumb_lo * row, n = (size_t)(c->thumb_hi - c->thumb_lo) * row;
-        tmp.resize(n);
-        hipError_t e = hipSetDevice(c->device);
-        if (e == hipSuccess) e = hipMemcpy(tmp.data(), c->d_thumb + first, n * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemsetAsync(c->d_thumb + first, 0, n * sizeof(unsigned long long), nullptr);
-        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);        // the slots' streams do not wait for the default stream
-        if (e != hipSuccess) { if (!rc) rc = hip_fail(e, "thumbnail read-back", AVIFGPU_writErr); continue; }
-        c->thumb_lo = c->thumb_hi = 0;
-        if (sums && tw == c->thumb_tw && th == c->thumb_th) for (size_t k = 0; k < n; ++k) sums[first + k] += tmp[k];
-    }
-    if (cur >= 0) (void)hipSetDevice(cur);
-    return rc;
-}
-// Likewise for the summary counters: max-merged into the calling thread's armed HOST counters.
-int collect_summaries(bool discard)
-{
-    uint32_t* counters = discard ? nullptr : summary_host_counters();
-    int cur = -1, rc = 0;
-    uint32_t tmp[AVIFGPU_SUMMARY_COUNTERS];
-    for (int i = 0; i < context_count(); ++i) {
-        Ctx* c = ctx_at(i);
-        if (!c->d_summary || !c->summary_dirty.load(std::memory_order_acquire)) continue;
-        if (cur == -1 && hipGetDevice(&cur) != hipSuccess) { (void)hipGetLastError(); cur = -2; }
-        hipError_t e = hipSetDevice(c->device);
-        if (e == hipSuccess) e = hipMemcpy(tmp, c->d_summary, sizeof(tmp), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemsetAsync(c->d_summary, 0, sizeof(tmp), nullptr);
-        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);        // the slots' streams do not wait for the default stream
-        if (e != hipSuccess) { if (!rc) rc = hip_fail(e, "summary read-back", AVIFGPU_writErr); continue; }
-        c->summary_dirty.store(false, std::memory_order_release);
-        if (counters) for (int k = 0; k < AVIFGPU_SUMMARY_COUNTERS; ++k) counters[k] = std::max(counters[k], tmp[k]);
+    std::vector<uint8_t> tmp;
+    for (int k = 0; k < 3; ++k) {
+        int krc = 0;
+        for (int i = 0; i < context_count(); ++i) {
+            Ctx* c = ctx_at(i);
+            DeviceAccum& a = k == 0 ? c->hist : k == 1 ? c->thumb : c->summary;
+            if (a.hi <= a.lo) continue;
+            if (cur == -1 && hipGetDevice(&cur) != hipSuccess) { (void)hipGetLastError(); cur = -2; }
+            const size_t first = a.lo;
+            hipError_t e = hipSetDevice(c->device);
+            if (e == hipSuccess) e = a.drain(tmp);
+            if (e != hipSuccess) { if (!krc) krc = hip_fail(e, kWhat[k], AVIFGPU_writErr); continue; }
+            const uint64_t* v64 = reinterpret_cast<const uint64_t*>(tmp.data());
+            const uint32_t* v32 = reinterpret_cast<const uint32_t*>(tmp.data());
+            if (k == 0 && to.hist) for (int b = 0; b < nbins; ++b) to.hist[b] += v64[b];
+            if (k == 1 && to.thumb && to.tw == c->thumb_tw && to.th == c->thumb_th)
+                for (size_t b = 0; b < tmp.size() / 8; ++b) to.thumb[first / 8 + b] += v64[b];
+            if (k == 2 && to.summary) for (int b = 0; b < AVIFGPU_SUMMARY_COUNTERS; ++b) to.summary[b] = std::max(to.summary[b], v32[b]);
+        }
+        if (!rc) rc = krc;
     }
     if (cur >= 0) (void)hipSetDevice(cur);
     return rc;
@@ -1152,11 +1107,7 @@ int wait_all_impl(bool discard_hist)
         if (c->err && !first) { first = c->err; snprintf(msg, sizeof(msg), "%s", c->err_msg); }
         c->err = 0; c->err_msg[0] = 0;
     }
-    int hrc = collect_histograms(discard_hist || first != 0);
-    const int trc = collect_thumbnails(discard_hist || first != 0);
-    if (!hrc) hrc = trc;
-    const int src = collect_summaries(discard_hist || first != 0);
-    if (!hrc) hrc = src;
+    const int hrc = collect(discard_hist || first != 0);
     if (first) set_error(msg);
     return first ? first : hrc;
 }

@@ -3,6 +3,7 @@
 //   pipeline.hip     the bound device contexts: one worker thread + N staging slots per context; row-tile scheduler
 //   host_shim.cpp    the FormatRecord tile protocol above them
 //   staged_open.cpp  the entry checks and the staged host path of the oriented, upsampled and cropped opens
+//   save_stats.cpp   the arming, the per-call check and the launch sequence of a save's three statistics
 // Nothing here crosses the C-ABI (include/avifgpu.h is the public surface).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -75,17 +76,28 @@ inline void label_cap(char* label, long long launched, long long need, long long
     const size_t n = strlen(label);
     if (n < (size_t)kLabelBytes) snprintf(label + n, kLabelBytes - n, " cap=%lld/%lld", launched, need);
 }
-// The calling thread's armed code histogram (avifgpu_histogram_attach): for a depth-32 write of `mem_kind`, 0 and *bins = the armed
-// counters (nullptr: nothing armed, or the descriptor is not counted), or formatBadParameters with a message when bit depth or memory kind disagree.
-int  histogram_for_call(const avifgpu_write_desc* d, int mem_kind, uint64_t** bins);
-uint64_t* histogram_host_bins(int* nbins);           // the calling thread's armed HOST counters, or nullptr
 
-// ---- thumbnail_kernels.hip: the box-average thumbnail of a save (avifgpu_thumbnail_attach) ---------------------------
-struct ThumbArm { uint64_t* sums; int tw, th; };     // sums == nullptr: nothing armed
-// The calling thread's arming for a write of `mem_kind`: 0 and *arm, or formatBadParameters with a message when the memory kind
-// disagrees or the geometry does not admit the armed size (tw / th above the smallest used plane's width / height).
-int  thumbnail_for_call(const avifgpu_write_desc* d, const WriteGeom& g, int mem_kind, ThumbArm* arm);
-uint64_t* thumbnail_host_sums(int* tw, int* th);     // the calling thread's armed HOST sums, or nullptr
+// ---- save_stats.cpp: the three statistics a save can carry -- the code histogram (avifgpu_histogram_attach), the thumbnail sums
+// (avifgpu_thumbnail_attach), the summary of the written planes (avifgpu_summary_attach) -- armed, checked and launched in one place ------
+// What is armed for one write call and where it goes.  A null target: not armed, or (the histogram) the descriptor is not counted.
+struct SaveStats {
+    uint64_t* hist = nullptr;                        // 1 << bit_depth bins
+    uint64_t* thumb = nullptr; int tw = 0, th = 0;   // [(ty * tw + tx) * planes + c]
+    uint32_t* summary = nullptr;                     // [AVIFGPU_SUMMARY_COUNTERS]
+    bool any() const { return hist || thumb || summary; }
+};
+// The calling thread's arms for a write of `mem_kind`: 0 and *s, or formatBadParameters with a message -- histogram first, then thumbnail,
+// then summary -- when an arm's memory kind disagrees, the histogram's bit depth is not the call's (depth-32 documents; others are not
+// counted), or the thumbnail is larger than the smallest used plane.
+int  save_stats_for_call(const avifgpu_write_desc* d, const WriteGeom& g, int mem_kind, SaveStats* s);
+// The calling thread's arms that live in HOST memory, whatever the descriptor (what wait_all() merges into); *nbins: the histogram's
+SaveStats save_stats_host(int* nbins);
+// The statistics kernels of one tile behind its launch_write() on `st`, in that order, into s's targets on the stream's device: `p` is what
+// that kernel was launched with (the histogram reads p.src again, the others the planes p.dst it wrote).  0 or writErr with a message.
+int  launch_save_stats(const avifgpu_write_desc* d, const WriteGeom& g, int row0, int nrows, const WriteParams& p, const SaveStats& s, hipStream_t st);
+
+// ---- thumbnail_kernels.hip: the box-average thumbnail of a save ------------------------------------------------------
+constexpr int kThumbMaxSide = 1024;
 // thumbnail rows [ty_lo, ty_hi) that source rows [row0, row0 + nrows) add to, over all planes
 void thumbnail_rows_of_tile(const avifgpu_write_desc* d, const WriteGeom& g, int row0, int nrows, int th, int& ty_lo, int& ty_hi);
 // Sum the output codes of one tile into sums[(ty * tw + tx) * planes + c], enqueued behind the tile's launch_write(): `planes` / `stride` are
@@ -93,11 +105,7 @@ void thumbnail_rows_of_tile(const avifgpu_write_desc* d, const WriteGeom& g, int
 hipError_t launch_thumbnail(const avifgpu_write_desc* d, const WriteGeom& g, int row0, int nrows, const uint8_t* const planes[4],
                             const int64_t stride[4], int tw, int th, unsigned long long* sums, hipStream_t st, int twin = 0);   // twin: avifgpu_probe_thumbnail
 
-// ---- summary_kernels.hip: the summary of a save's written planes (avifgpu_summary_attach) ----------------------------
-// The calling thread's arming for a write of `mem_kind`: 0 and *counters (nullptr: nothing armed), or formatBadParameters with a
-// message when the memory kind disagrees.
-int  summary_for_call(int mem_kind, uint32_t** counters);
-uint32_t* summary_host_counters();                   // the calling thread's armed HOST counters, or nullptr
+// ---- summary_kernels.hip: the summary of a save's written planes -----------------------------------------------------
 // Raise counters[AVIFGPU_SUMMARY_COUNTERS] by the output codes of one tile, enqueued behind the tile's launch_write(): `planes` / `stride`
 // are the pointers that kernel wrote through (at row row0; chroma: row0 >> ys), counters lives on the stream's device.
 hipError_t launch_summary(const avifgpu_write_desc* d, const WriteGeom& g, int row0, int nrows, const uint8_t* const planes[4],
@@ -175,9 +183,8 @@ int  write_tile_enqueue(int ctx, int slot, const avifgpu_write_desc* d, int row0
 int  read_tile_enqueue(int ctx, int slot, const avifgpu_read_desc* d, int row0, int nrows, const void* const src[4],
                        const int64_t src_stride[4], void* dst, int64_t dst_row_bytes);
 int  wait_slot(int ctx, int slot);                   // the tile last queued on (ctx, slot) has fully landed in host memory
-int  wait_all();                                     // every context idle; returns the first error any tile produced.  Tiles that counted into their
-                                                     // contexts' code histograms: the sums are added to `hist_bins` of the calling thread (nothing on an error)
-                                                     // (thumbnail sums and summary counters likewise: added / max-merged into the calling thread's, nothing on an error)
+int  wait_all();                                     // every context idle; returns the first error any tile produced.  What the tiles added to their
+                                                     // contexts' statistics accumulators is merged into the calling thread's HOST arms (nothing on an error)
 // One host-pointer conversion (whole-range call or a shim save / open) at a time per process: they share slots and error state.
 void host_call_lock();
 void host_call_unlock();

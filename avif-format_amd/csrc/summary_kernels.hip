@@ -28,6 +28,7 @@
 
 #include "staging.h"
 #include "kernel_params.h"
+#include "written_planes.h"
 
 namespace avifgpu {
 
@@ -215,12 +216,6 @@ __global__ __launch_bounds__(kSumThreads) void plane_summary(const SummaryParams
     }
 }
 
-// the calling thread's arming (avifgpu_summary_attach): host-only bookkeeping, survives a re-binding of the devices
-thread_local uint32_t* g_sum_counters = nullptr;
-thread_local int g_sum_kind = AVIFGPU_MEM_HOST;
-
-int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
 bool gbr_planes(const avifgpu_write_desc* d, const WriteGeom& g)
 {
     return d->output == AVIFGPU_OUT_YCBCR && d->matrix_coefficients == AVIFGPU_MATRIX_RGB_GBR && g.xs == 0 && g.ys == 0;
@@ -244,10 +239,7 @@ hipError_t launch_layout(SummaryParams& p, hipStream_t st)
     if (max_rows <= 0 || max_bytes <= 0) return hipSuccess;
     if (max_bytes >= (int64_t)1 << 31) return hipErrorInvalidValue;               // the kernel indexes a row's bytes in 32 bits
     const int gx = (int)ceil_div64(max_bytes, (int64_t)kSumThreads * S::CHUNK);
-    // bands as launch_thumbnail cuts them: about 8192 workgroups over all planes, at least 8 rows each, no more bands than grid.y allows
-    const int64_t bands_wanted = std::max<int64_t>(1, 8192 / ((int64_t)gx * p.nslots));
-    int64_t band_rows = std::max<int64_t>(8, ceil_div64(max_rows, bands_wanted));
-    band_rows = std::max<int64_t>(band_rows, ceil_div64(max_rows, 65535));
+    const int64_t band_rows = band_rows_for(gx, p.nslots, max_rows);
     p.band_rows = (int)band_rows;
     const dim3 grid((unsigned)gx, (unsigned)ceil_div64(max_rows, band_rows), (unsigned)p.nslots), block(kSumThreads);
     hipLaunchKernelGGL((plane_summary<T, LAYOUT>), grid, block, 0, st, p);
@@ -261,58 +253,37 @@ template <int LAYOUT> hipError_t launch_layout_t(bool dst16, SummaryParams& p, h
 
 } // namespace
 
-int summary_for_call(int mem_kind, uint32_t** counters)
-{
-    *counters = nullptr;
-    if (!g_sum_counters) return 0;
-    if (mem_kind != g_sum_kind)
-        return fail(AVIFGPU_formatBadParameters, "the armed summary counters live in %s memory, this call's pointers do not",
-                    g_sum_kind == AVIFGPU_MEM_DEVICE ? "device" : "host");
-    *counters = g_sum_counters;
-    return 0;
-}
-
-uint32_t* summary_host_counters()
-{
-    return g_sum_kind == AVIFGPU_MEM_HOST ? g_sum_counters : nullptr;
-}
-
 hipError_t launch_summary(const avifgpu_write_desc* d, const WriteGeom& g, int row0, int nrows, const uint8_t* const planes[4],
                           const int64_t stride[4], uint32_t* counters, hipStream_t st, int twin)
 {
-    (void)row0;                                                                   // the planes come at the tile's first row
     if (nrows <= 0) return hipSuccess;
     SummaryParams p;
     memset(&p, 0, sizeof(p));
     p.counters = counters; p.twin = twin;
-    auto add = [&](int plane, int c0, int nplanes) {                              // nplanes 3: the G,B,R planes read together
+    WrittenPlane wp[4];
+    const int n = written_planes(d, g, row0, nrows, planes, stride, wp);
+    auto add = [&](int first, int joined) {                                       // joined 3: the G,B,R planes read together as one slot
         SummaryPlane& t = p.pl[p.nslots++];
-        const bool chroma = d->output == AVIFGPU_OUT_YCBCR && (c0 == 1 || c0 == 2);
-        t.pw = chroma ? (d->width + g.xs) >> g.xs : d->width;
-        t.prows = chroma ? (nrows + g.ys) >> g.ys : nrows;
-        t.c0 = c0;
-        uintptr_t bits = 0;
-        for (int l = 0; l < nplanes; ++l) {
-            t.base[l] = planes[plane + l]; t.stride[l] = stride[plane + l];
-            bits |= reinterpret_cast<uintptr_t>(t.base[l]) | (uintptr_t)t.stride[l];
+        t.pw = wp[first].pw; t.prows = wp[first].prows; t.c0 = wp[first].c0; t.aligned = 1;
+        for (int l = 0; l < joined; ++l) {
+            const WrittenPlane& w = wp[first + l];
+            t.base[l] = planes[w.plane]; t.stride[l] = stride[w.plane];
+            t.aligned &= (int)w.aligned;
         }
-        t.aligned = (bits & 15) == 0;
     };
     if (d->output == AVIFGPU_OUT_REFERENCE && g.color) {
-        add(0, 0, 1);
+        add(0, 1);
         return d->planes == 3 ? launch_layout_t<kInter3>(g.dst16, p, st) : launch_layout_t<kInter4>(g.dst16, p, st);
     }
-    if (d->output == AVIFGPU_OUT_REFERENCE) { add(0, 0, 1); if (g.alpha) add(3, 1, 1); return launch_layout_t<kPlanar>(g.dst16, p, st); }
-    if (gbr_planes(d, g)) {
-        add(0, 0, 3);
-        const hipError_t e = launch_layout_t<kGbr>(g.dst16, p, st);
-        if (e != hipSuccess || !g.alpha) return e;
-        p.nslots = 0;
-        add(3, 3, 1);
+    if (!gbr_planes(d, g)) {
+        for (int i = 0; i < n; ++i) add(i, 1);
         return launch_layout_t<kPlanar>(g.dst16, p, st);
     }
-    add(0, 0, 1); add(1, 1, 1); add(2, 2, 1);
-    if (g.alpha) add(3, 3, 1);
+    add(0, 3);
+    const hipError_t e = launch_layout_t<kGbr>(g.dst16, p, st);
+    if (e != hipSuccess || !g.alpha) return e;
+    p.nslots = 0;
+    add(3, 1);
     return launch_layout_t<kPlanar>(g.dst16, p, st);
 }
 
@@ -322,16 +293,6 @@ hipError_t launch_summary(const avifgpu_write_desc* d, const WriteGeom& g, int r
 using namespace avifgpu;
 
 extern "C" {
-
-int32_t avifgpu_summary_attach(uint32_t* counters, int32_t mem_kind)
-{
-    set_error("");
-    if (!counters) { g_sum_counters = nullptr; g_sum_kind = AVIFGPU_MEM_HOST; return 0; }
-    if (mem_kind != AVIFGPU_MEM_HOST && mem_kind != AVIFGPU_MEM_DEVICE)
-        return fail(AVIFGPU_formatBadParameters, "avifgpu_summary_attach: bad mem_kind %d", mem_kind);
-    g_sum_counters = counters; g_sum_kind = mem_kind;
-    return 0;
-}
 
 int32_t avifgpu_summary_merge(uint32_t* into, const uint32_t* from)
 {
@@ -393,12 +354,7 @@ int32_t avifgpu_probe_summary(const avifgpu_write_desc* desc, int32_t twin, cons
     if (!planes || !stride || !counters) return fail(AVIFGPU_formatBadParameters, "avifgpu_probe_summary: null argument");
     if (twin < 0 || twin > 1) return fail(AVIFGPU_formatBadParameters, "avifgpu_probe_summary: twin %d is not 0 or 1", twin);
     const uint8_t* pp[4];
-    for (int pl = 0; pl < 4; ++pl) {
-        pp[pl] = static_cast<const uint8_t*>(planes[pl]);
-        if (!write_plane_used(desc, g, pl)) continue;
-        int rows; int64_t rb; write_plane_extent(desc, g, pl, desc->height, rows, rb);
-        if (!pp[pl] || stride[pl] < rb) return fail(AVIFGPU_formatBadParameters, "avifgpu_probe_summary: plane %d is null or its stride too small", pl);
-    }
+    if ((err = check_probe_planes("avifgpu_probe_summary", desc, g, planes, stride, pp))) return err;
     if (context_count() == 0) return fail(AVIFGPU_formatBadParameters, "avifgpu_init has not succeeded: no HIP device bound (no CPU fallback)");
     const hipError_t e = launch_summary(desc, g, 0, desc->height, pp, stride, counters, (hipStream_t)stream, twin);
     return e == hipSuccess ? 0 : hip_fail(e, "avifgpu_probe_summary", AVIFGPU_writErr);

@@ -26,6 +26,7 @@
 
 #include "staging.h"
 #include "kernel_params.h"
+#include "written_planes.h"
 
 namespace avifgpu {
 
@@ -41,7 +42,6 @@ constexpr int kThumbLaneBytes = 16;
 // cells than pixels (tw <= pw): at most 1366 x 3 = 4098 counters.  launch_thumbnail sizes the dynamic LDS by the first bound, capped by this.
 constexpr int kThumbEntries = 4096 + 8;
 constexpr int kThumbMaxBandRows = 32768;          // see "No wrap" above
-constexpr int kThumbMaxSide = 1024;
 
 // a / b for a < 2^42, b < 2^31: 32-bit when the dividend allows it (every plane narrower than 2^22 pixels)
 __device__ __forceinline__ uint32_t tb_div(uint64_t a, uint32_t b)
@@ -248,48 +248,7 @@ __global__ __launch_bounds__(kThumbThreads) void thumb_box_sums(const ThumbParam
     }
 }
 
-// the calling thread's arming (avifgpu_thumbnail_attach): host-only bookkeeping, survives a re-binding of the devices
-thread_local uint64_t* g_thumb_sums = nullptr;
-thread_local int g_thumb_tw = 0, g_thumb_th = 0, g_thumb_kind = AVIFGPU_MEM_HOST;
-
-int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-// width / height of output channel c of the whole image, and the smallest over the channels
-bool channel_extent(const avifgpu_write_desc* d, const WriteGeom& g, int c, int& pw, int& ph)      // true: a chroma plane
-{
-    const bool chroma = d->output == AVIFGPU_OUT_YCBCR && (c == 1 || c == 2);
-    pw = chroma ? (d->width + g.xs) >> g.xs : d->width;
-    ph = chroma ? (d->height + g.ys) >> g.ys : d->height;
-    return chroma;
-}
-void smallest_plane(const avifgpu_write_desc* d, const WriteGeom& g, int& pw, int& ph)
-{
-    pw = d->width; ph = d->height;
-    if (d->output == AVIFGPU_OUT_YCBCR) channel_extent(d, g, 1, pw, ph);
-}
-
 } // namespace
-
-int thumbnail_for_call(const avifgpu_write_desc* d, const WriteGeom& g, int mem_kind, ThumbArm* arm)
-{
-    arm->sums = nullptr; arm->tw = arm->th = 0;
-    if (!g_thumb_sums) return 0;
-    if (mem_kind != g_thumb_kind)
-        return fail(AVIFGPU_formatBadParameters, "the armed thumbnail sums live in %s memory, this call's pointers do not",
-                    g_thumb_kind == AVIFGPU_MEM_DEVICE ? "device" : "host");
-    int pw, ph;
-    smallest_plane(d, g, pw, ph);
-    if (g_thumb_tw > pw || g_thumb_th > ph)
-        return fail(AVIFGPU_formatBadParameters, "the armed thumbnail is %dx%d, the smallest plane of this save %dx%d", g_thumb_tw, g_thumb_th, pw, ph);
-    arm->sums = g_thumb_sums; arm->tw = g_thumb_tw; arm->th = g_thumb_th;
-    return 0;
-}
-
-uint64_t* thumbnail_host_sums(int* tw, int* th)
-{
-    *tw = g_thumb_tw; *th = g_thumb_th;
-    return g_thumb_kind == AVIFGPU_MEM_HOST ? g_thumb_sums : nullptr;
-}
 
 void thumbnail_rows_of_tile(const avifgpu_write_desc* d, const WriteGeom& g, int row0, int nrows, int th, int& ty_lo, int& ty_hi)
 {
@@ -319,30 +278,21 @@ hipError_t launch_thumbnail(const avifgpu_write_desc* d, const WriteGeom& g, int
     int max_rows = 0;
     int64_t max_samples = 0, max_entries = 0;
     const int64_t blk = (int64_t)(kThumbLaneBytes / ssz) * kThumbThreads;
-    auto add = [&](int plane, int c0) {
-        ThumbPlane& t = p.pl[p.nslots++];
-        const bool chroma = channel_extent(d, g, c0, t.pw, t.ph);
-        t.base = planes[plane]; t.stride = stride[plane];
-        t.prow0 = chroma ? row0 >> g.ys : row0;
-        t.prows = chroma ? (nrows + g.ys) >> g.ys : nrows;
-        t.c0 = c0;
-        t.aligned = ((reinterpret_cast<uintptr_t>(t.base) | (uintptr_t)t.stride) & 15) == 0;
+    WrittenPlane wp[4];
+    p.nslots = written_planes(d, g, row0, nrows, planes, stride, wp);
+    for (int i = 0; i < p.nslots; ++i) {
+        const WrittenPlane& w = wp[i];
+        ThumbPlane& t = p.pl[i];
+        t.base = planes[w.plane]; t.stride = stride[w.plane];
+        t.pw = w.pw; t.ph = w.ph; t.prow0 = w.prow0; t.prows = w.prows; t.c0 = w.c0; t.aligned = w.aligned;
         max_rows = std::max(max_rows, t.prows);
         max_samples = std::max<int64_t>(max_samples, (int64_t)t.pw * nch);
         max_entries = std::max<int64_t>(max_entries, (((blk / nch + 1) * tw) / t.pw + 2) * nch);     // see kThumbEntries
-    };
-    if (interleaved) add(0, 0);
-    else if (d->output == AVIFGPU_OUT_REFERENCE) { add(0, 0); if (g.alpha) add(3, 1); }
-    else { add(0, 0); add(1, 1); add(2, 2); if (g.alpha) add(3, 3); }
+    }
     if (max_samples * ssz >= (int64_t)1 << 31) return hipErrorInvalidValue;        // the kernel indexes a row's samples in 32 bits
     p.lds_entries = (int)std::min<int64_t>(max_entries, kThumbEntries);
     const int gx = (int)ceil_div64(max_samples, blk);
-    // bands: about 8192 workgroups over all planes -- several rounds of what the chip holds at once, so that the last round's ragged end is
-    // a small part of the run -- but at least 8 rows each so that a lane's loads stay in flight four deep, and no more bands than grid.y
-    // allows; band_rows <= kThumbMaxBandRows keeps the 32-bit register sums from wrapping
-    const int64_t bands_wanted = std::max<int64_t>(1, 8192 / ((int64_t)gx * p.nslots));
-    int64_t band_rows = std::max<int64_t>(8, ceil_div64(max_rows, bands_wanted));
-    band_rows = std::max<int64_t>(band_rows, ceil_div64(max_rows, 65535));
+    const int64_t band_rows = band_rows_for(gx, p.nslots, max_rows);       // <= kThumbMaxBandRows keeps the 32-bit register sums from wrapping
     if (band_rows > kThumbMaxBandRows) return hipErrorInvalidValue;                // unreachable: max_rows < 2^31 = 65535 * 32768 + ...
     p.band_rows = (int)band_rows;
     const dim3 grid((unsigned)gx, (unsigned)ceil_div64(max_rows, band_rows), (unsigned)p.nslots), block(kThumbThreads);
@@ -359,18 +309,6 @@ hipError_t launch_thumbnail(const avifgpu_write_desc* d, const WriteGeom& g, int
 using namespace avifgpu;
 
 extern "C" {
-
-int32_t avifgpu_thumbnail_attach(uint64_t* sums, int32_t tw, int32_t th, int32_t mem_kind)
-{
-    set_error("");
-    if (!sums) { g_thumb_sums = nullptr; g_thumb_tw = g_thumb_th = 0; g_thumb_kind = AVIFGPU_MEM_HOST; return 0; }
-    if (tw < 1 || tw > kThumbMaxSide || th < 1 || th > kThumbMaxSide)
-        return fail(AVIFGPU_formatBadParameters, "avifgpu_thumbnail_attach: size %dx%d outside 1..%d", tw, th, kThumbMaxSide);
-    if (mem_kind != AVIFGPU_MEM_HOST && mem_kind != AVIFGPU_MEM_DEVICE)
-        return fail(AVIFGPU_formatBadParameters, "avifgpu_thumbnail_attach: bad mem_kind %d", mem_kind);
-    g_thumb_sums = sums; g_thumb_tw = tw; g_thumb_th = th; g_thumb_kind = mem_kind;
-    return 0;
-}
 
 int32_t avifgpu_thumbnail_fit(const avifgpu_write_desc* desc, int32_t bbox, int32_t* tw, int32_t* th)
 {
@@ -456,12 +394,7 @@ int32_t avifgpu_probe_thumbnail(const avifgpu_write_desc* desc, int32_t twin, in
     if (tw < 1 || th < 1 || tw > kThumbMaxSide || th > kThumbMaxSide || tw > pw || th > ph)
         return fail(AVIFGPU_formatBadParameters, "avifgpu_probe_thumbnail: size %dx%d outside 1..%d or above the smallest plane %dx%d", tw, th, kThumbMaxSide, pw, ph);
     const uint8_t* pp[4];
-    for (int pl = 0; pl < 4; ++pl) {
-        pp[pl] = static_cast<const uint8_t*>(planes[pl]);
-        if (!write_plane_used(desc, g, pl)) continue;
-        int rows; int64_t rb; write_plane_extent(desc, g, pl, desc->height, rows, rb);
-        if (!pp[pl] || stride[pl] < rb) return fail(AVIFGPU_formatBadParameters, "avifgpu_probe_thumbnail: plane %d is null or its stride too small", pl);
-    }
+    if ((err = check_probe_planes("avifgpu_probe_thumbnail", desc, g, planes, stride, pp))) return err;
     if (context_count() == 0) return fail(AVIFGPU_formatBadParameters, "avifgpu_init has not succeeded: no HIP device bound (no CPU fallback)");
     const hipError_t e = launch_thumbnail(desc, g, 0, desc->height, pp, stride, tw, th, reinterpret_cast<unsigned long long*>(sums), (hipStream_t)stream, twin);
     return e == hipSuccess ? 0 : hip_fail(e, "avifgpu_probe_thumbnail", AVIFGPU_writErr);
