@@ -291,13 +291,22 @@ AG_DEV f32x2 fast_linear_to_pq01_2_hi(f32x2 value, float mult)
 //
 // As written this cancels catastrophically (c2 - c3 x = 18.85 - 18.69x with x in [0.9, 1]): one ulp of x moves the
 // result by up to 4.5e-5 relative, which is also the reference's own float noise floor.  Here delta = 1 - x =
-// -expm1(ln(v)/m2) is evaluated directly (|ln(v)/m2| <= 0.16 for every non-zero 12-bit code), and with
+// -expm1(ln(v)/m2) is evaluated directly (|ln(v)/m2| <= 0.106 for every non-zero 12-bit code; for the arguments of a YCbCr open see below), and with
 // 1 - c1 = c2 - c3 = 0.1640625 exactly:  x - c1 = 0.1640625 - delta,  c2 - c3 x = 0.1640625 + c3 delta.
 // log2_mult = log2(10000 / peak): the final "* luminanceMultiplier" is folded into the last exponent.
 // Cost: 4 quarter-rate transcendentals + 14 full-rate ops per sample.
-// Round 4: the series stops at t^5 / 120 (|t| <= 0.106 for every non-zero 12-bit code: the dropped terms are below 2e-8 of delta;
-// t = -0.5, the stand-in for v <= 0, still gives delta = 0.39 > 1 - c1 and the exact 0), and there is a form for TWO samples whose
-// full-rate operations are packed (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32: element for element the scalar sequence, same bits).
+// Round 4: the series stops at t^5 / 120, and there is a form for TWO samples whose full-rate operations are packed (v_pk_fma_f32 /
+// v_pk_mul_f32 / v_pk_add_f32: element for element the scalar sequence, same bits).
+// The range of t.  A table value i / max (planar RGB, gray) has |t| <= 0.106 at 12 bit.  The argument of a YCbCr open is NOT a code
+// value: it is clamp(Y + c * Cr) (over A when unpremultiplied) and falls anywhere in (0, 1 / max) too -- the 12-bit BT.2020 Latin square
+// holds 5 859 such samples, the smallest 2.2e-8 (t = -0.223); a non-zero clamped sum of table floats is at least 2^-40 (see
+// unpremultiply_one, read_kernels.hip), t = -0.352; v <= 0 takes the stand-in t = -0.5.  What the series has to deliver:
+//   t in [ln(c1), 0] = [-0.179, 0] (v >= c1^m2 = 7.3e-7): the dropped terms, t^6 / 720 on, are below 4.6e-8 absolute, 2.8e-7 of delta;
+//   t in [-0.5, -0.179): only delta >= 1 - c1, so that num clamps to the exact 0 the reference returns there.  The dropped terms are
+//     positive in e^t, so the series' delta is never below the true one (0.164 at -0.179, 0.39 at -0.5): the zero region is kept.
+// Measured on the device over whole code domains (tests/test_zz_gpu_whole_float_opens.py, profiles/float_opens/): against float64
+// truth of the same float32 argument the worst relative error of any colour sample is 5.0e-6, and 4.4e-6 on the samples with
+// 0 < v < 1 / max; the packed form gives the scalar form's bits on every argument the two were both given.
 AG_DEV float fast_pq_to_linear_l2(float value, float log2_mult)
 {
     // t = ln(v)/m2.  v <= 0 or NaN give -inf / NaN from v_log_f32; v_max_f32 turns both into -0.5, where
