@@ -162,6 +162,16 @@ class CropRect(ctypes.Structure):
         return (self.x0, self.y0, self.width, self.height)
 
 
+class Grid(ctypes.Structure):
+    """avifgpu_grid: columns x rows tiles of tile_width x tile_height, row-major."""
+    _fields_ = [("columns", c_int32), ("rows", c_int32), ("tile_width", c_int32), ("tile_height", c_int32)]
+
+
+class GridTile(ctypes.Structure):
+    """avifgpu_grid_tile: the planes of one decoded tile (64 bytes)."""
+    _fields_ = [("plane", c_void_p * 4), ("stride", c_int64 * 4)]
+
+
 class ContentLightLevel(ctypes.Structure):
     """avifgpu_content_light_level: the clli fields and what they were rounded from."""
     _fields_ = [("max_cll", ctypes.c_uint16), ("max_fall", ctypes.c_uint16), ("max_code", c_int32), ("pixels", ctypes.c_uint64),
@@ -276,6 +286,13 @@ ABI = [
     ("avifgpu_read_rows_cropped", c_int32, [POINTER(ReadDesc), POINTER(CropRect), c_int32, c_int32, c_int32, c_int32, POINTER(_PLANES4), POINTER(_STRIDES4),
                                             c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p]),
     ("avifgpu_probe_crop", c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p]),
+    ("avifgpu_grid_parse", c_int32, [c_void_p, c_int64, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
+    ("avifgpu_grid_check", c_int32, [POINTER(ReadDesc), POINTER(Grid)]),
+    ("avifgpu_read_grid_scratch_bytes", c_int64, [POINTER(ReadDesc), POINTER(Grid), POINTER(CropRect), c_int32, c_int32, c_int32]),
+    ("avifgpu_read_rows_grid", c_int32, [POINTER(ReadDesc), POINTER(Grid), c_void_p, POINTER(CropRect), c_int32, c_int32, c_int32, c_int32,
+                                         c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p]),
+    ("avifgpu_probe_grid_gather", c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                            c_void_p, c_int64, c_void_p]),
 ]
 
 
@@ -297,7 +314,9 @@ ABI4_NEW = frozenset(("avifgpu_probe_pattern_read", "avifgpu_probe_pattern_rgb32
                       "avifgpu_host_read_heif_image_upsampled",   # (the upsampled open)
                       "avifgpu_clap_to_rect", "avifgpu_crop_compose", "avifgpu_read_cropped_geometry", "avifgpu_read_cropped_next_tile",
                       "avifgpu_read_cropped_scratch_bytes", "avifgpu_read_rows_cropped", "avifgpu_probe_crop",
-                      "avifgpu_host_read_heif_image_cropped"))   # (the cropped open)
+                      "avifgpu_host_read_heif_image_cropped",   # (the cropped open)
+                      "avifgpu_grid_parse", "avifgpu_grid_check", "avifgpu_read_grid_scratch_bytes", "avifgpu_read_rows_grid",
+                      "avifgpu_probe_grid_gather", "avifgpu_host_read_heif_image_grid"))   # (the grid open)
 
 
 def bind(lib: ctypes.CDLL, table=ABI) -> ctypes.CDLL:
@@ -463,6 +482,20 @@ class AvifGpu:
         self._check(self.lib.avifgpu_read_rows_cropped(ctypes.byref(desc), ctypes.byref(crop_rect(rect)), upsampling, orientation, orow0, onrows,
                                                        ctypes.byref(planes4(src_ptrs)), ctypes.byref(strides4(src_strides)),
                                                        dst_ptr, dst_row_bytes, scratch_ptr or None, scratch_bytes, mem, stream or None))
+
+    def read_rows_grid(self, desc: ReadDesc, grid, tiles, rect, upsampling, orientation, orow0, onrows, dst_ptr, dst_row_bytes,
+                       scratch_ptr=None, scratch_bytes=0, mem=MEM_DEVICE, stream=0):
+        """Output rows [orow0, orow0 + onrows) of the cropped (upsampled, oriented) open of a grid image (avifgpu_read_rows_grid): tiles is
+        the address of columns * rows GridTile records where `mem` says (or a ctypes array of them for MEM_HOST); rect None: the whole canvas."""
+        if isinstance(tiles, ctypes.Array):
+            tiles = ctypes.addressof(tiles)
+        self._check(self.lib.avifgpu_read_rows_grid(ctypes.byref(desc), ctypes.byref(grid_of(grid)), tiles or None,
+                                                    ctypes.byref(crop_rect(rect)) if rect is not None else None, upsampling, orientation, orow0, onrows,
+                                                    dst_ptr, dst_row_bytes, scratch_ptr or None, scratch_bytes, mem, stream or None))
+
+    def probe_grid_gather(self, tiles_dev, columns, plane, tile_w, tile_h, bytes_per_sample, x0, y0, w, h, dst, dst_row_bytes, stream=None):
+        """Launch the grid gather kernel alone on one plane (avifgpu_probe_grid_gather)."""
+        self._check(self.lib.avifgpu_probe_grid_gather(tiles_dev, columns, plane, tile_w, tile_h, bytes_per_sample, x0, y0, w, h, dst, dst_row_bytes, stream))
 
     def probe_crop(self, src, src_row_bytes, dst, dst_row_bytes, row_payload_bytes, rows, stream=None):
         """Launch the crop mover kernel alone on device buffers (avifgpu_probe_crop)."""
@@ -762,6 +795,30 @@ def read_cropped_next_tile(desc: ReadDesc, rect, upsampling: int, orientation: i
 def read_cropped_scratch_bytes(desc: ReadDesc, rect, upsampling: int, orientation: int, onrows: int) -> int:
     """Device scratch that is enough for any MEM_DEVICE call of onrows output rows of the cropped open (avifgpu_read_cropped_scratch_bytes)."""
     return _oserr(load().avifgpu_read_cropped_scratch_bytes(ctypes.byref(desc), ctypes.byref(crop_rect(rect)), upsampling, orientation, onrows))
+
+
+def grid_of(grid) -> Grid:
+    """A Grid from (columns, rows, tile_width, tile_height) or a Grid."""
+    return grid if isinstance(grid, Grid) else Grid(*grid)
+
+
+def grid_parse(payload: bytes) -> tuple:
+    """(rows, columns, output_width, output_height) of an ImageGrid item payload (avifgpu_grid_parse)."""
+    r, c, w, h = (c_int32() for _ in range(4))
+    buf = ctypes.create_string_buffer(bytes(payload), max(len(payload), 1))
+    _oserr(load().avifgpu_grid_parse(ctypes.addressof(buf), len(payload), ctypes.byref(r), ctypes.byref(c), ctypes.byref(w), ctypes.byref(h)))
+    return r.value, c.value, w.value, h.value
+
+
+def grid_check(desc: ReadDesc, grid) -> None:
+    """Raise unless (desc, grid) is what the grid open takes (avifgpu_grid_check)."""
+    _oserr(load().avifgpu_grid_check(ctypes.byref(desc), ctypes.byref(grid_of(grid))))
+
+
+def read_grid_scratch_bytes(desc: ReadDesc, grid, rect, upsampling: int, orientation: int, onrows: int) -> int:
+    """Device scratch of a MEM_DEVICE call of onrows output rows of the grid open (avifgpu_read_grid_scratch_bytes)."""
+    return _oserr(load().avifgpu_read_grid_scratch_bytes(ctypes.byref(desc), ctypes.byref(grid_of(grid)),
+                                                          ctypes.byref(crop_rect(rect)) if rect is not None else None, upsampling, orientation, onrows))
 
 
 def read_oriented_scratch_bytes(desc: ReadDesc, orientation: int, onrows: int) -> int:

@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/avifgpu_host.h"
@@ -42,6 +43,7 @@ struct Args {
     int matrix = AVIFGPU_MATRIX_BT601, primaries = AVIFGPU_PRIMARIES_BT709, tc = 2, limited = 0, colorspace = AVIFGPU_COLORSPACE_YCBCR;
     int lossless = 0, maxdata = 0, device = 0, hlg_ootf = 0, nclx = 0, keep_profile = 0, light_level = 0, thumb_bbox = 0, summary = 0, orientation = 0, upsampling = AVIFGPU_UPSAMPLE_NEAREST;
     int crop = 0, crop_x0 = 0, crop_y0 = 0, crop_w = 0, crop_h = 0;
+    int grid = 0, grid_cols = 0, grid_rows = 0, grid_tw = 0, grid_th = 0;
     float gamma = 1.2f;
     double percentile = 1.0;
 };
@@ -57,7 +59,9 @@ struct Args {
         "       avifgpu_cli read  --width W --height H --depth 8|16|32 --bits 8|10|12 --colorspace ycbcr|rgb|mono [--chroma 444|422|420]\n"
         "                         [--alpha none|straight|premultiplied] [--matrix N --primaries N --tc N [--limited]] [--peak NITS]\n"
         "                         [--hlg-ootf --gamma G] [--orientation 1..8] [--chroma-upsampling nearest|bilinear|bilinear-left]\n"
-        "                         [--crop X0,Y0,W,H] [--maxdata BYTES] [--device N] IN.planes OUT.raw\n");
+        "                         [--crop X0,Y0,W,H] [--grid COLSxROWS,TWxTH] [--maxdata BYTES] [--device N] IN.planes OUT.raw\n"
+        "       --grid: IN.planes holds the tiles' planes, tile after tile in row-major order, each laid out like a whole image of TW x TH;\n"
+        "               --width / --height are the canvas\n");
     exit(2);
 }
 
@@ -106,6 +110,7 @@ Args parse(int argc, char** argv)
         else if (o == "--ycbcr") { a.output = AVIFGPU_OUT_YCBCR; a.chroma = pick(val(), {{"444", AVIFGPU_CHROMA_444}, {"422", AVIFGPU_CHROMA_422}, {"420", AVIFGPU_CHROMA_420}}, "--ycbcr"); }
         else if (o == "--chroma") a.chroma = pick(val(), {{"444", AVIFGPU_CHROMA_444}, {"422", AVIFGPU_CHROMA_422}, {"420", AVIFGPU_CHROMA_420}}, "--chroma");
         else if (o == "--colorspace") a.colorspace = pick(val(), {{"ycbcr", AVIFGPU_COLORSPACE_YCBCR}, {"rgb", AVIFGPU_COLORSPACE_RGB}, {"mono", AVIFGPU_COLORSPACE_MONOCHROME}}, "--colorspace");
+        else if (o == "--grid") { a.grid = 1; if (sscanf(val(), "%dx%d,%dx%d", &a.grid_cols, &a.grid_rows, &a.grid_tw, &a.grid_th) != 4) usage("--grid needs COLSxROWS,TWxTH"); }
         else if (o == "--help" || o == "-h") usage(nullptr);
         else if (o.rfind("--", 0) == 0) usage(("unknown option " + o).c_str());
         else pos.push_back(o);
@@ -280,8 +285,55 @@ int do_write(const Args& a)
     return 0;
 }
 
+// --grid: the tiles of a grid image, opened without assembling the canvas on the CPU (avifgpu_host_read_heif_image_grid)
+int do_read_grid(const Args& a)
+{
+    if (a.grid_cols < 1 || a.grid_cols > 256 || a.grid_rows < 1 || a.grid_rows > 256 || a.grid_tw < 1 || a.grid_th < 1) { fprintf(stderr, "avifgpu_cli: bad --grid\n"); return 2; }
+    std::vector<avifgpu_image> tiles((size_t)a.grid_cols * a.grid_rows);
+    auto release = [&]() { for (avifgpu_image& t : tiles) if (t.owner) avifgpu_image_free(&t); };
+    FILE* in = fopen(a.in.c_str(), "rb");
+    if (!in) { perror(a.in.c_str()); return 1; }
+    for (avifgpu_image& t : tiles) {
+        t = avifgpu_image{};
+        t.width = a.grid_tw; t.height = a.grid_th; t.colorspace = a.colorspace; t.bit_depth = a.bits;
+        t.chroma = a.colorspace == AVIFGPU_COLORSPACE_MONOCHROME ? AVIFGPU_CHROMA_MONOCHROME : a.colorspace == AVIFGPU_COLORSPACE_RGB ? AVIFGPU_CHROMA_444 : a.chroma;
+        t.has_alpha = a.alpha != AVIFGPU_ALPHA_NONE; t.premultiplied_alpha = a.alpha == AVIFGPU_ALPHA_PREMULTIPLIED;
+        if (avifgpu_image_alloc(&t) != AVIFGPU_noErr) { fprintf(stderr, "avifgpu_cli: out of memory\n"); fclose(in); release(); return 1; }
+        for (int pl = 0; pl < 4; ++pl) {
+            if (!t.plane[pl]) continue;
+            const size_t rb = plane_row_bytes(t, pl);
+            for (int y = 0; y < plane_rows(t, pl); ++y)
+                if (fread(t.plane[pl] + (size_t)y * t.stride[pl], 1, rb, in) != rb) { fprintf(stderr, "avifgpu_cli: %s is too short\n", a.in.c_str()); fclose(in); release(); return 1; }
+        }
+    }
+    fclose(in);
+    const int planes = (a.colorspace == AVIFGPU_COLORSPACE_MONOCHROME ? 1 : 3) + (a.alpha != AVIFGPU_ALPHA_NONE ? 1 : 0);
+    setup_record(a, planes);
+    const avifgpu_rect rect{a.crop_x0, a.crop_y0, a.crop_w, a.crop_h};
+    int vw = a.crop ? a.crop_w : a.width, vh = a.crop ? a.crop_h : a.height;
+    if (a.orientation >= 5) std::swap(vw, vh);
+    g_host.fr.imageSize32 = {vh, vw};
+    g_host.fr.imageSize = {(int16_t)(vh > 32767 ? 32767 : vh), (int16_t)(vw > 32767 ? 32767 : vw)};
+    g_host.file = fopen(a.out.c_str(), "wb");
+    if (!g_host.file) { perror(a.out.c_str()); release(); return 1; }
+    g_host.saving = false;
+    avifgpu_nclx nclx{a.primaries, a.tc, a.matrix, (uint8_t)!a.limited};
+    avifgpu_LoadUIOptions lo{};
+    lo.pq.nominalPeakBrightness = a.peak; lo.hlg.applyOOTF = (uint8_t)a.hlg_ootf; lo.hlg.displayGamma = a.gamma; lo.hlg.nominalPeakBrightness = a.peak;
+    const avifgpu_grid grid{a.grid_cols, a.grid_rows, a.grid_tw, a.grid_th};
+    const int rc = avifgpu_host_read_heif_image_grid(tiles.data(), &grid, a.width, a.height, a.crop ? &rect : nullptr, a.orientation ? a.orientation : 1, a.upsampling, a.alpha,
+                                                     (a.nclx || a.depth == 32) ? &nclx : nullptr, &lo, &g_host.fr);
+    fclose(g_host.file);
+    release();
+    if (rc) return fail("avifgpu_host_read_heif_image_grid", rc);
+    fprintf(stderr, "read: %dx%d canvas in %dx%d tiles of %dx%d, %d-bit -> host depth %d, %d planes, %d tiles, maxValue %d\n", a.width, a.height, a.grid_cols, a.grid_rows,
+            a.grid_tw, a.grid_th, a.bits, a.depth, planes, g_host.tiles, g_host.fr.maxValue);
+    return 0;
+}
+
 int do_read(const Args& a)
 {
+    if (a.grid) return do_read_grid(a);
     avifgpu_image img{};
     img.width = a.width; img.height = a.height; img.colorspace = a.colorspace; img.bit_depth = a.bits;
     img.chroma = a.colorspace == AVIFGPU_COLORSPACE_MONOCHROME ? AVIFGPU_CHROMA_MONOCHROME

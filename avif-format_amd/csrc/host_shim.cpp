@@ -21,6 +21,7 @@
 #include <memory>
 #include <new>
 #include <stdexcept>
+#include <vector>
 
 #include "../../include/avifgpu_host.h"
 #include "staging.h"
@@ -476,6 +477,59 @@ void ReadHeifImageCropped(const avifgpu_image* image, const avifgpu_rect& rect, 
     formatRecord->data = nullptr;
 }
 
+// The grid open (avifgpu_read_rows_grid): `tiles` are the decoded tile items of a grid image in row-major order, the canvas is width x
+// height, the document is orient(code, F[rect]) of the assembled canvas.  As above, with the same cuts.
+void ReadHeifImageGrid(const avifgpu_image* tiles, const avifgpu_grid& grid, int width, int height, const avifgpu_rect* rectOrNull, int orientation, int upsampling,
+                       AlphaState alphaState, const avifgpu_nclx* nclxProfile, const LoadUIOptions* loadOptions, FormatRecordPtr formatRecord)
+{
+    const VPoint imageSize = GetImageSize(formatRecord);
+    if (orientation < 1 || orientation > 8) { avifgpu::set_error("orientation is not an EXIF code 1..8"); throw OSErrException(AVIFGPU_formatBadParameters); }
+    if (upsampling < AVIFGPU_UPSAMPLE_NEAREST || upsampling > AVIFGPU_UPSAMPLE_BILINEAR_LEFT) { avifgpu::set_error("chroma upsampling is not an AVIFGPU_UPSAMPLE_* value"); throw OSErrException(AVIFGPU_formatBadParameters); }
+    if (width < 1 || height < 1 || grid.columns < 1 || grid.columns > 256 || grid.rows < 1 || grid.rows > 256) { avifgpu::set_error("bad canvas size, or columns and rows are not 1..256"); throw OSErrException(AVIFGPU_formatBadParameters); }
+    const avifgpu_rect whole = { 0, 0, width, height };
+    const avifgpu_rect rect = rectOrNull ? *rectOrNull : whole;
+    if (rect.x0 < 0 || rect.y0 < 0 || rect.width < 1 || rect.height < 1 || (int64_t)rect.x0 + rect.width > width || (int64_t)rect.y0 + rect.height > height) {
+        avifgpu::set_error("the rectangle is not inside the canvas"); throw OSErrException(AVIFGPU_formatBadParameters);
+    }
+    const bool turned = orientation >= 5;
+    if (imageSize.h != (turned ? rect.height : rect.width) || imageSize.v != (turned ? rect.width : rect.height)) {
+        avifgpu::set_error("the document's size is not the cropped, oriented size of the canvas (avifgpu_read_cropped_geometry)");
+        throw OSErrException(AVIFGPU_formatBadParameters);
+    }
+    VPoint stored;
+    stored.h = width; stored.v = height;
+    const avifgpu_read_desc d = PrepareRead(&tiles[0], alphaState, nclxProfile, loadOptions, formatRecord, imageSize, stored);
+    if (avifgpu_grid_check(&d, &grid)) throw OSErrException(AVIFGPU_formatBadParameters);
+    std::vector<avifgpu_grid_tile> table((size_t)grid.columns * grid.rows);
+    for (size_t k = 0; k < table.size(); ++k) {
+        const avifgpu_image& t = tiles[k];
+        if (t.colorspace != tiles[0].colorspace || t.chroma != tiles[0].chroma || t.bit_depth != tiles[0].bit_depth || t.width != grid.tile_width || t.height != grid.tile_height) {
+            avifgpu::set_error("a tile differs from tile 0 in colourspace, chroma format or bit depth, or is not tile_width x tile_height"); throw OSErrException(AVIFGPU_formatBadParameters);
+        }
+        for (int pl = 0; pl < 4; ++pl) { table[k].plane[pl] = t.plane[pl]; table[k].stride[pl] = t.stride[pl]; }
+    }
+    if (avifgpu::context_count() == 0) { avifgpu::set_error("avifgpu_init has not succeeded: no HIP device bound (no CPU fallback)"); throw OSErrException(AVIFGPU_formatBadParameters); }
+
+    const int maxRows = rows_per_tile(formatRecord->maxData, formatRecord->rowBytes, imageSize.v, false);
+    void* const tile = avifgpu::tile_buffer(0, 0, (size_t)maxRows * (size_t)formatRecord->rowBytes);
+    if (!tile) throw std::bad_alloc();
+    auto bail = [&](OSErr e) { formatRecord->data = nullptr; throw OSErrException(e); };
+    const int32_t left = 0, right = imageSize.h;
+    for (int32_t top = 0; top < imageSize.v;) {
+        if (formatRecord->abortProc && formatRecord->abortProc()) bail(AVIFGPU_userCanceledErr);
+        const int32_t n = avifgpu_read_cropped_next_tile(&d, &rect, upsampling, orientation, top, maxRows);
+        if (n <= 0) bail(n < 0 ? (OSErr)n : AVIFGPU_readErr);
+        const int err = avifgpu_read_rows_grid(&d, &grid, table.data(), &rect, upsampling, orientation, top, n, tile, formatRecord->rowBytes, nullptr, 0, AVIFGPU_MEM_HOST, nullptr);
+        if (err) bail((OSErr)err);
+        formatRecord->data = tile;
+        SetRect(formatRecord, top, left, top + n, right);
+        const OSErr herr = formatRecord->advanceState();
+        if (herr != AVIFGPU_noErr) bail(herr);
+        top += n;
+    }
+    formatRecord->data = nullptr;
+}
+
 // Exception -> OSErr exactly as the Do* drivers do it (Write.cpp:345-364, Read.cpp:659-678).
 template <typename F> OSErr guarded(F&& f, OSErr fallback)
 {
@@ -643,6 +697,17 @@ avifgpu_OSErr avifgpu_host_read_heif_image_cropped(const avifgpu_image* image, c
     return guarded([&] {
         avifgpu::HostCallGuard serial;
         ReadHeifImageCropped(image, *rect, orientation, upsampling, (AlphaState)alphaState, nclxProfile, loadOptions, formatRecord);
+    }, AVIFGPU_readErr);
+}
+
+avifgpu_OSErr avifgpu_host_read_heif_image_grid(const avifgpu_image* tiles, const avifgpu_grid* grid, int32_t width, int32_t height, const avifgpu_rect* rect,
+                                                int32_t orientation, int32_t upsampling, int32_t alphaState, const avifgpu_nclx* nclxProfile,
+                                                const avifgpu_LoadUIOptions* loadOptions, avifgpu_FormatRecord* formatRecord)
+{
+    if (!tiles || !grid || !formatRecord || !formatRecord->advanceState) return AVIFGPU_formatBadParameters;
+    return guarded([&] {
+        avifgpu::HostCallGuard serial;
+        ReadHeifImageGrid(tiles, *grid, width, height, rect, orientation, upsampling, (AlphaState)alphaState, nclxProfile, loadOptions, formatRecord);
     }, AVIFGPU_readErr);
 }
 

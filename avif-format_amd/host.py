@@ -95,6 +95,8 @@ HOST_ABI = [
                                                          POINTER(FormatRecord)]),
     ("avifgpu_host_read_heif_image_cropped", c_int16, [POINTER(Image), c_void_p, c_int32, c_int32, c_int32, POINTER(Nclx), POINTER(LoadUIOptions),
                                                        POINTER(FormatRecord)]),      # c_void_p: const avifgpu_rect* (CropRect of the package)
+    ("avifgpu_host_read_heif_image_grid", c_int16, [POINTER(Image), c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32, POINTER(Nclx),
+                                                    POINTER(LoadUIOptions), POINTER(FormatRecord)]),   # c_void_p: const avifgpu_grid*, const avifgpu_rect* (Grid, CropRect of the package)
     # decisions of the reference-named adapters (csrc/host_decisions.cpp)
     ("avifgpu_host_image_bit_depth", c_int32, [c_int32]),
     ("avifgpu_host_chroma_subsampling", c_int32, [c_int32, c_int32]),

@@ -946,6 +946,70 @@ int32_t avifgpu_read_rows_cropped(const avifgpu_read_desc* desc, const avifgpu_r
 int32_t avifgpu_probe_crop(const void* src, int64_t src_row_bytes, void* dst, int64_t dst_row_bytes, int64_t row_payload_bytes, int32_t rows,
                            void* stream);
 
+/* ---- grid open: a tiled (grid) image opened from its decoded tiles ----------------------------------------------------------------------
+ * Large AVIF / HEIF pictures are stored as a `grid` derived image (ISO 23008-12 6.6.2.3): columns x rows coded tiles of tile_width x
+ * tile_height in row-major order, of which the top-left desc.width x desc.height is visible.  libheif assembles the canvas on the CPU
+ * inside heif_decode_image; an adapter that decodes the tile items itself hands their planes over as they are.  Every tile has the
+ * colourspace, chroma format, bit depth and set of planes of the descriptor; the alpha plane shares the colour planes' tiling (an alpha
+ * auxiliary image with a tiling of its own stays the caller's to assemble).  With xs, ys the chroma shifts, a tile's plane pl holds
+ * tw_p x th_p samples -- (tile_width, tile_height) for luma, alpha, R, G, B; ((tile_width + xs) >> xs, (tile_height + ys) >> ys) for
+ * chroma -- and the ASSEMBLED plane is
+ *     P_pl[y, x] = tile[(y / th_p) * columns + (x / tw_p)].plane[pl][y % th_p, x % tw_p]
+ * over the canvas's plane extent (chroma: ((W + xs) >> xs) x ((H + ys) >> ys)).  The grid open of (rect, upsampling, code, orow0, onrows)
+ * IS avifgpu_read_rows_cropped on the assembled planes, byte for byte, for every descriptor that entry takes: float hosts, padding rules
+ * and out-of-range sample rules included.  Assembly comes before upsampling, so bilinear taps cross tile seams as they cross any other
+ * sample boundary.  That libheif 1.14.0 assembles a grid exactly this way is believed and NOT verified.
+ * Legal grids: 1 <= columns, rows <= 256; columns * tile_width >= width and rows * tile_height >= height (in 64 bits); tile_width even
+ * where columns are subsampled and columns > 1; tile_height even where rows are subsampled and rows > 1. */
+typedef struct avifgpu_grid      { int32_t columns, rows, tile_width, tile_height; } avifgpu_grid;
+typedef struct avifgpu_grid_tile { const void* plane[4]; int64_t stride[4]; } avifgpu_grid_tile;   /* 64 bytes */
+
+/* The ImageGrid item payload, big-endian: version(8) = 0, flags(8), rows_minus_one(8), columns_minus_one(8), output_width and
+ * output_height as 16 bits each, or 32 bits each when flags & 1 -- 8 or 12 bytes; trailing bytes are ignored.  formatBadParameters for a
+ * null argument, a version other than 0, a short payload, a zero size, a size above INT32_MAX.  Host only: needs no device. */
+int32_t avifgpu_grid_parse(const uint8_t* payload, int64_t size, int32_t* rows, int32_t* columns, int32_t* out_w, int32_t* out_h);
+
+/* 0 where desc (its width x height is the canvas) and grid are what avifgpu_read_rows_grid takes; formatBadParameters (or what the
+ * descriptor's own check returns) otherwise.  Host only. */
+int32_t avifgpu_grid_check(const avifgpu_read_desc* desc, const avifgpu_grid* grid);
+
+/* Device scratch that every MEM_DEVICE call of `onrows` output rows needs -- the entry asks for exactly this value.  rect NULL: the whole
+ * canvas.  With the source region of those rows sw x sh (rect.width x onrows for codes 1-4, onrows x rect.height for codes 5-8), s bytes
+ * per plane sample, gw = min(width, sw + 38), gh = min(height, sh + 6) (the cropped open's staged rectangle never exceeds that: the
+ * region, its covering row / column or bilinear halo, and up to 31 columns in front of it):
+ *     256  +  sum over the used planes of  align256(gw_p * s) * gh_p  +  C
+ * where (gw_p, gh_p) = (gw, gh), for the chroma planes of a subsampled image ((gw + xs) >> xs, (gh + ys) >> ys), and C is
+ * avifgpu_read_cropped_scratch_bytes' formula for sw x sh with px and py both counted.  The 256 let the library start on a 256-byte
+ * boundary whatever `scratch` is.  A negative OSErr for an unknown enum, a bad descriptor, grid or rectangle.  Host only. */
+int64_t avifgpu_read_grid_scratch_bytes(const avifgpu_read_desc* desc, const avifgpu_grid* grid, const avifgpu_rect* rect, int32_t upsampling,
+                                        int32_t orientation, int32_t onrows);
+
+/* Open output rows [orow0, orow0 + onrows) of the cropped (upsampled, oriented) ASSEMBLED image.  Cuts and the output size are the cropped
+ * open's (avifgpu_read_cropped_next_tile, avifgpu_read_cropped_geometry on desc): every cut is legal and the bytes of a tile do not depend
+ * on the tiling of the output rows.  rect NULL: the whole canvas.  `tiles` holds columns * rows records and lives where mem_kind says:
+ *   AVIFGPU_MEM_DEVICE  a device pointer to records of device pointers.  The library never reads it on the host: grid_gather -- one launch
+ *     of a byte-moving kernel, a code object of its own -- writes the staged rectangle of every used plane (what the cropped open's host
+ *     path would upload for these rows) into the head of scratch, and avifgpu_read_rows_cropped runs on that with the rest of scratch.
+ *     Everything is enqueued on `stream`; nothing synchronises.  A 1 x 1 grid gathers too.
+ *   AVIFGPU_MEM_HOST    a host array of host pointers; scratch is ignored.  A 1 x 1 grid is avifgpu_read_rows_cropped on tile 0.  Otherwise
+ *     the call is staged in tiles through two slots of the library's own on the FIRST bound context: each plane rectangle goes up as one
+ *     strided copy per intersecting tile, straight into its place, so the copy engine assembles and no gather kernel runs.  The bytes are
+ *     the same for every number of bound contexts, pinned or pageable memory.
+ * A tile with no visible sample is never read and its pointers may be NULL; on MEM_HOST a NULL pointer or a stride below the row for a
+ * used plane of a visible tile is rejected.  formatBadParameters before anything is launched for an illegal grid, NULL tiles, a bad
+ * rectangle, upsampling, code or row range, less scratch than the helper's value, too small dst_row_bytes. */
+int32_t avifgpu_read_rows_grid(const avifgpu_read_desc* desc, const avifgpu_grid* grid, const avifgpu_grid_tile* tiles,
+                               const avifgpu_rect* rect, int32_t upsampling, int32_t orientation, int32_t orow0, int32_t onrows,
+                               void* dst, int64_t dst_row_bytes, void* scratch, int64_t scratch_bytes, int32_t mem_kind, void* stream);
+
+/* Measuring and testing aid (tools/bench_grid.py): the gather kernel ALONE on one plane -- rectangle [x0, x0 + w) x [y0, y0 + h) of the
+ * plane assembled from tiles_dev[...].plane[plane] (tile_w_samples x tile_h_samples each, `columns` to a row; the rectangle must lie
+ * inside the tiles the table holds) into rows of dst, on `stream`.  dst and dst_row_bytes are multiples of 16; bytes of a dst row beyond
+ * the payload are not touched. */
+int32_t avifgpu_probe_grid_gather(const avifgpu_grid_tile* tiles_dev, int32_t columns, int32_t plane, int32_t tile_w_samples,
+                                  int32_t tile_h_samples, int32_t bytes_per_sample, int32_t x0, int32_t y0, int32_t w, int32_t h,
+                                  void* dst, int64_t dst_row_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -212,6 +212,17 @@ avifgpu_OSErr avifgpu_host_read_heif_image_cropped(const avifgpu_image* image, c
                                                    int32_t alphaState, const avifgpu_nclx* nclxProfile, const avifgpu_LoadUIOptions* loadOptions,
                                                    avifgpu_FormatRecord* formatRecord);
 
+/* A tiled (grid) image opened from its decoded tiles (avifgpu_read_rows_grid, include/avifgpu.h): `tiles` are the grid->columns * grid->rows
+ * tile items in row-major order, each tile_width x tile_height with the colourspace, chroma format and bit depth of tile 0, else
+ * AVIFGPU_formatBadParameters; the planes of a tile with no visible sample may be NULL.  The canvas is width x height (the ImageGrid
+ * payload's output size, avifgpu_grid_parse); rect (NULL: the whole canvas), orientation and upsampling as for
+ * avifgpu_host_read_heif_image_cropped, and formatRecord's image size must be the cropped, oriented size of the canvas.  Tiles of the
+ * DOCUMENT go top to bottom, are sized from maxData and cut with avifgpu_read_cropped_next_tile; abortProc is asked before every one. */
+avifgpu_OSErr avifgpu_host_read_heif_image_grid(const avifgpu_image* tiles, const avifgpu_grid* grid, int32_t width, int32_t height,
+                                                const avifgpu_rect* rect, int32_t orientation, int32_t upsampling, int32_t alphaState,
+                                                const avifgpu_nclx* nclxProfile, const avifgpu_LoadUIOptions* loadOptions,
+                                                avifgpu_FormatRecord* formatRecord);
+
 /* ==== Decisions of the reference-named adapters, as C-ABI helpers =====================================================
  * Everything integration/WriteHeifImage_gpu.cpp / ReadHeifImage_gpu.cpp (the twelve reference-named functions, compiled only
  * against the real Photoshop SDK + libheif headers) has to DECIDE lives here, where it is compiled and tested without those
