@@ -3,7 +3,7 @@
 // One definition for both sides: icc_pipeline32.cpp evaluates it on the host (the proof's engine, avifgpu_icc_pipeline32_eval), the
 // write kernel (write_px<..., icc = 8>, write_kernels.hip) per pixel.  Where the two sides differ it is in HOW a value is formed, never in
 // which value: the 16-bit word of a float (the library's double expression on the host, quick_saturate_word_f32 on the device -- equal
-// for every float, tools/satword_check.hip) and w / 65535.0 as a float (equal for all 65536 words, tests/test_gpu_icc.py).  pow() is the
+// for every float that is a number, tools/satword_check.hip; a NaN's word from its payload bits on both sides) and w / 65535.0 as a float (equal for all 65536 words, tests/test_gpu_icc.py).  pow() is the
 // platform's: the host calls the C library lcms2 calls, the device OCML's (within an ulp of double: tier 2 behind the transfer curve).
 #pragma once
 #if defined(__HIPCC__)
@@ -35,6 +35,9 @@ constexpr double kD50X = 0.9642, kD50Y = 1.0, kD50Z = 0.8249;
 ICC32_HD uint32_t sat_word(float v)
 {
 #ifdef __HIP_DEVICE_COMPILE__
+    // A NaN takes neither saturation of the library's form below: its word is the floor of the low half of the double NaN, which holds
+    // the three low payload bits of the float (32767 for the default NaN).  quick_saturate_word_f32 clamps a NaN to 0.
+    if (v != v) return (uint32_t)(((int32_t)(__float_as_uint(v) << 29) >> 16) + 32767) & 0xffffu;
     return quick_saturate_word_f32(v);
 #else
     double d = (double)v * 65535.0 + 0.5;

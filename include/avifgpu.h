@@ -702,8 +702,12 @@ int32_t avifgpu_write_rows_icc8_table(const avifgpu_write_desc* desc, const avif
  * AVIFGPU_formatCannotRead and keeps lcms2.  A program is PROVEN before use: avifgpu_icc_pipeline32_prove evaluates the library's host
  * restatement on a fixed probe set and requires bit-identical floats from the caller's own cmsDoTransform; only then is it stamped, and
  * avifgpu_write_rows_icc_pipeline32 refuses an unstamped or altered program.  (The write kernel evaluates the same program -- curves and
- * matrices in double, the words with the library's arithmetic -- tier 2 like every float path: the bar is on the integer codes behind
- * the transfer curve.) */
+ * matrices in double, the words with the library's arithmetic.  Held exactly: for a program without pow() -- table curves, the CLUT,
+ * matrices, Lab -> XYZ, gamma-1 curves -- the kernel's float after the last stage is the float avifgpu_icc_pipeline32_eval gives, for every
+ * input, NaN (whose 16-bit word lcms2 takes from its payload bits), +-Inf and values far outside [0, 1] included: the codes of the save equal
+ * those of a save without ICC of the host's floats.  Behind pow() or the cube root of XYZ -> Lab the float may be a float32 neighbour of the
+ * host's -- the device's pow() is not the C library's --, which is tier 2 like every float path: the bar is on the integer codes behind
+ * the transfer curve.  tests/test_zzzz_gpu_icc32_programs.py.) */
 enum { AVIFGPU_ICC_PIPE_MAX_STAGES = 16, AVIFGPU_ICC_PIPE_MAX_CURVE = 4096, AVIFGPU_ICC_PIPE_MAX_GRID = 33,
        AVIFGPU_ICC_PIPE_MAX_WORDS = 33 * 33 * 33 * 3 + 4 * 3 * 4096 };
 enum { AVIFGPU_ICC_STAGE_CURVES = 1, AVIFGPU_ICC_STAGE_MATRIX = 2, AVIFGPU_ICC_STAGE_CLUT16 = 3,

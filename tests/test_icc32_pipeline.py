@@ -168,80 +168,7 @@ def test_eval_rejects_a_malformed_program():
 
 
 # ---- profiles built with lcms2 inside the test -------------------------------------------------------------------------------------
-def _sig(s):
-    return int.from_bytes(s.encode(), "big")
-
-
-def _lcms2_lib(L):
-    """The liblcms2 the ICC oracle links (already loaded with it)."""
-    C = ctypes.CDLL("liblcms2.so.2")
-    vp, u32 = ctypes.c_void_p, ctypes.c_uint32
-    for name, res, args in [("cmsCreateContext", vp, [vp, vp]), ("cmsDeleteContext", None, [vp]),
-                            ("cmsCreateProfilePlaceholder", vp, [vp]), ("cmsCloseProfile", ctypes.c_int, [vp]),
-                            ("cmsSetProfileVersion", None, [vp, ctypes.c_double]), ("cmsSetDeviceClass", None, [vp, u32]),
-                            ("cmsSetColorSpace", None, [vp, u32]), ("cmsSetPCS", None, [vp, u32]),
-                            ("cmsPipelineAlloc", vp, [vp, u32, u32]), ("cmsPipelineFree", None, [vp]),
-                            ("cmsPipelineInsertStage", ctypes.c_int, [vp, ctypes.c_int, vp]),
-                            ("cmsStageAllocToneCurves", vp, [vp, u32, vp]),
-                            ("cmsStageAllocCLut16bit", vp, [vp, u32, u32, u32, vp]),
-                            ("cmsStageAllocCLutFloat", vp, [vp, u32, u32, u32, vp]),
-                            ("cmsBuildTabulatedToneCurve16", vp, [vp, u32, vp]), ("cmsFreeToneCurve", None, [vp]),
-                            ("cmsWriteTag", ctypes.c_int, [vp, u32, vp]), ("cmsD50_XYZ", vp, []),
-                            ("cmsSaveProfileToMem", ctypes.c_int, [vp, vp, ctypes.POINTER(u32)])]:
-        fn = getattr(C, name)
-        fn.restype, fn.argtypes = res, args
-    return C
-
-
-def _lut_profile(L, tag, grid, float_clut=False, table_curves=0):
-    """A v4 RGB display profile (PCS Lab) holding one LUT tag: [curves] -> CLUT (grid^3, 16-bit or float) -> [curves].  The CLUT maps
-    device RGB to a Lab ramp so that the transform exists; table_curves > 0 makes the curves 16-bit tables of that many entries."""
-    C = _lcms2_lib(L)
-    ctx = C.cmsCreateContext(None, None)
-    h = C.cmsCreateProfilePlaceholder(ctx)
-    C.cmsSetProfileVersion(h, 4.3)
-    C.cmsSetDeviceClass(h, _sig("mntr"))
-    C.cmsSetColorSpace(h, _sig("RGB "))
-    C.cmsSetPCS(h, _sig("Lab "))
-    lut = C.cmsPipelineAlloc(ctx, 3, 3)
-    g = np.linspace(0.0, 1.0, grid)
-    r, gg, b = np.meshgrid(g, g, g, indexing="ij")
-    lab = np.stack([0.05 + 0.9 * (0.3 * r + 0.6 * gg + 0.1 * b), 0.5 + 0.2 * (r - gg), 0.5 + 0.2 * (gg - b)], axis=-1).reshape(-1)
-    curves = None
-    if table_curves:
-        t = np.round(np.linspace(0.0, 1.0, table_curves) ** 1.1 * 65535).astype(np.uint16)
-        c = C.cmsBuildTabulatedToneCurve16(ctx, table_curves, t.ctypes.data)
-        curves = (ctypes.c_void_p * 3)(c, c, c)
-    if not float_clut:                                      # (a multi-process-element tag holds segmented curves only: none there)
-        C.cmsPipelineInsertStage(lut, 1, C.cmsStageAllocToneCurves(ctx, 3, curves))
-    if float_clut:
-        tab = lab.astype(np.float32)
-        clut = C.cmsStageAllocCLutFloat(ctx, grid, 3, 3, tab.ctypes.data)
-    else:
-        tab = np.round(lab * 65535).astype(np.uint16)
-        clut = C.cmsStageAllocCLut16bit(ctx, grid, 3, 3, tab.ctypes.data)
-    assert clut
-    C.cmsPipelineInsertStage(lut, 1, clut)
-    if not float_clut:
-        C.cmsPipelineInsertStage(lut, 1, C.cmsStageAllocToneCurves(ctx, 3, None))
-    assert C.cmsWriteTag(h, _sig(tag), lut) and C.cmsWriteTag(h, _sig("wtpt"), C.cmsD50_XYZ())
-    if tag != "A2B0":                                       # a float LUT tag goes WITH an A2B0 (which lcms2 then ignores)
-        lut16 = C.cmsPipelineAlloc(ctx, 3, 3)
-        C.cmsPipelineInsertStage(lut16, 1, C.cmsStageAllocToneCurves(ctx, 3, None))
-        C.cmsPipelineInsertStage(lut16, 1, C.cmsStageAllocCLut16bit(ctx, 2, 3, 3, None))
-        C.cmsPipelineInsertStage(lut16, 1, C.cmsStageAllocToneCurves(ctx, 3, None))
-        assert C.cmsWriteTag(h, _sig("A2B0"), lut16)
-        C.cmsPipelineFree(lut16)
-    n = ctypes.c_uint32(0)
-    assert C.cmsSaveProfileToMem(h, None, ctypes.byref(n))
-    buf = ctypes.create_string_buffer(n.value)
-    assert C.cmsSaveProfileToMem(h, buf, ctypes.byref(n))
-    if table_curves:
-        C.cmsFreeToneCurve(c)
-    C.cmsPipelineFree(lut)
-    C.cmsCloseProfile(h)
-    C.cmsDeleteContext(ctx)
-    return buf.raw[:n.value]
+from icc32_programs import lut_profile as _lut_profile  # noqa: E402  (shared with the stage-program tests)
 
 
 @pytest.mark.parametrize("target", TARGETS)
