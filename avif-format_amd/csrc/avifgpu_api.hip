@@ -5,17 +5,12 @@
 // (one worker thread + staging slots per context, row tiles dealt across contexts); device-pointer calls
 // launch directly on the caller's stream and device.
 #include <hip/hip_runtime.h>
-#include <atomic>
 #include <cstddef>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <limits>
-#include <map>
-#include <mutex>
-#include <vector>
 
 #include "../../include/avifgpu.h"
 #include "kernel_params.h"
@@ -162,415 +157,17 @@ int check_write(const avifgpu_write_desc* d, int row0, int nrows, WriteGeom& g)
     return 0;
 }
 
-// Device copies of the ICC tables, one set per HIP device (the row-tile scheduler converts one image on several GPUs).
-// Re-uploaded only when the contents change (one image = one upload per device); a change first drains that device so no
-// in-flight kernel still reads the old tables.  Callers run on the thread whose CURRENT device is the one they launch on.
-struct IccDeviceTables {
-    void* icc8 = nullptr;  std::vector<uint8_t> icc8_host;     // [3][256] int32 followed by 16388 bytes of shaper2
-    void* icc16 = nullptr; std::vector<uint8_t> icc16_host;    // 33^3 x 4 u16
-    void* pow_tab = nullptr;                                    // 128 x float4, constant
-    void* s32 = nullptr;   std::vector<uint8_t> s32_host;      // 3 x 65536 floats: sampled curves of a 32-bit document
-    void* p32 = nullptr;   std::vector<uint8_t> p32_host;      // stage records + words of a 32-bit document's stage program (icc = 8)
-    // the caller's table of the last upload and a fingerprint of it: a tile that passes the same struct again (every tile of an image
-    // does) skips the byte-for-byte comparison of 216-792 KiB under g_icc_mu.  A prepared table is immutable while it is in use
-    // (include/avifgpu.h); the fingerprint -- 4096 strided words -- is the guard against a caller that rewrites one in place anyway,
-    // and it is trusted WITHIN an image only (round 5, ADVICE r04: a caller may legally rewrite or reallocate a table at the same address
-    // between two saves, and a change the stride misses -- 32 consecutive floats of a 4096-entry curve -- would otherwise keep the stale
-    // device copy).  "Within an image" is an EPOCH, not "row0 != 0" (round 6): the tables are cached per device and a
-    // multi-GPU save hands row 0 to one device only, so the first tile EACH device sees in an epoch takes the full comparison.  The
-    // epoch advances with every call that does not continue the calling thread's previous one row for row (a new image, a rank's own
-    // tile of the next image, tiles out of order) -- icc_epoch_for_call() below.
-    const void* s32_src = nullptr;   uint64_t s32_fp = 0;   uint64_t s32_epoch = 0;
-    const void* icc16_src = nullptr; uint64_t icc16_fp = 0; uint64_t icc16_epoch = 0;
-};
-static std::atomic<uint64_t> g_icc_epoch{1};
-// Called once per C-ABI write call (or shim tile) that carries an ICC table, on the caller's thread, before any tile is dealt.  Only a call
-// that CONTINUES the calling thread's previous one -- row0 == the row after its last -- stays in its epoch: the tiles of one save, handed over
-// top to bottom.  Anything else (row 0, a restart, a gap, tiles out of order, another geometry) starts a new epoch and costs each device
-// one byte-for-byte comparison of the table.
-void icc_epoch_for_call(int row0, int nrows)
-{
-    thread_local long long next_row = -1;
-    if (row0 == 0 || (long long)row0 != next_row) g_icc_epoch.fetch_add(1, std::memory_order_relaxed);
-    next_row = (long long)row0 + nrows;
-}
-static uint64_t table_fingerprint(const void* base, size_t bytes)
-{
-    const uint32_t* w = static_cast<const uint32_t*>(base);
-    const size_t n = bytes / 4, step = n / 4096 ? n / 4096 : 1;
-    uint64_t h = 1469598103934665603ull ^ (uint64_t)bytes;
-    for (size_t i = 0; i < n; i += step) h = (h ^ w[i]) * 1099511628211ull;
-    if (n) h = (h ^ w[n - 1]) * 1099511628211ull;
-    return h;
-}
-static std::mutex g_icc_mu;
-static std::map<int, IccDeviceTables> g_icc_tables;            // keyed by HIP device ordinal
-
-// The bins of icc_pow32 (write_kernels.hip): c = RN_float(1 / bin centre) and -log2(c) as a float pair.  Constants -- evaluated
-// once per device here instead of once per workgroup on the device (a double log2 there costs ~200 instructions per thread, a
-// quarter of what a streaming workgroup does in its whole life).
-int upload_icc_pow_table(WriteParams& p)
-{
-    int dev = -1;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return hip_fail(e, "hipGetDevice", AVIFGPU_writErr);
-    std::lock_guard<std::mutex> lk(g_icc_mu);
-    IccDeviceTables& c = g_icc_tables[dev];
-    if (!c.pow_tab) {
-        float t[128][4];
-        for (int i = 0; i < 128; ++i) {
-            const double centre = 0.5 + ((double)i + 0.5) * (1.0 / 256.0);
-            const float cf = (float)(1.0 / centre);
-            const double L = -std::log2((double)cf);
-            const float Lh = (float)L;
-            t[i][0] = cf; t[i][1] = Lh; t[i][2] = (float)(L - (double)Lh); t[i][3] = 0.0f;
-        }
-        e = hipMalloc(&c.pow_tab, sizeof(t));
-        if (e == hipSuccess) e = hipMemcpy(c.pow_tab, t, sizeof(t), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { if (c.pow_tab) (void)hipFree(c.pow_tab); c.pow_tab = nullptr; return hip_fail(e, "upload of the pow table", AVIFGPU_memFullErr); }
-    }
-    p.icc_pow_tab = static_cast<const float*>(c.pow_tab);
-    return 0;
-}
-
-int upload_icc16(const avifgpu_icc_clut16* t, WriteParams& p)
-{
-    if (t->grid_points != AVIFGPU_ICC_CLUT_GRID) return fail(AVIFGPU_formatBadParameters, "16-bit ICC table: grid_points must be 33");
-    const size_t n = sizeof(t->table);
-    // Device layout (kernel_params.h, AG_ICC16_DOT2): node-PAIR tables, 1.76 MB -- the four nodes of a pixel's tetrahedron arrive in two
-    // 12-byte gathers, {p0, p3} from table A and {p1, p2} from table B, each pair stored channel by channel (lo | hi << 16), the operand
-    // form of v_dot2_u32_u16.  Nodes beyond the grid are zero: the fraction of an axis at its end is 0 and so is their weight, which is
-    // what the library's zeroed strides amount to.  Round 2 and the first half of round 3 used one 128-byte RECORD per cell (every
-    // node stored up to eight times, 4.6 MB: two gathers from one line, but the table did not stay in the 4 MB L2 next to the streams
-    // and uniformly random input re-fetched it from the Infinity Cache at 2.4 x the algorithmic traffic; layout 1 below, kept for A/B).
-    constexpr size_t G = AVIFGPU_ICC_CLUT_GRID;
-    [[maybe_unused]] constexpr size_t kRecU16 = kIcc16RecBytes / 2;       // (layout 1 only)
-    const size_t rec_bytes = AG_ICC16_DOT2 == 2 ? (size_t)kIcc16PairTablesBytes : G * G * G * kIcc16RecBytes;
-    int dev = -1;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return hip_fail(e, "hipGetDevice", AVIFGPU_writErr);
-    std::lock_guard<std::mutex> lk(g_icc_mu);
-    IccDeviceTables& c = g_icc_tables[dev];
-    if (!c.icc16) {
-        e = hipMalloc(&c.icc16, rec_bytes);
-        if (e != hipSuccess) { c.icc16 = nullptr; return hip_fail(e, "hipMalloc(icc16 table)", AVIFGPU_memFullErr); }
-    }
-    const uint64_t fp = table_fingerprint(t->table, n);
-    const uint64_t epoch = g_icc_epoch.load(std::memory_order_relaxed);
-    const bool same_call = c.icc16_epoch == epoch && c.icc16_src == t && c.icc16_fp == fp && c.icc16_host.size() == n;
-    if (!same_call && (c.icc16_host.size() != n || memcmp(c.icc16_host.data(), t->table, n) != 0)) {
-        std::vector<uint16_t> rec(rec_bytes / 2, 0);
-#if AG_ICC16_DOT2 == 2
-        // node-pair tables (kernel_params.h): A[n] = {node n, node n + (1,1,1)}, B[3 m + k] = {node m, node m + e_k}
-        {
-            auto node_at = [&](size_t r, size_t g, size_t b) -> const uint16_t* {
-                return (r < G && g < G && b < G) ? t->table[(r * G + g) * G + b] : nullptr;
-            };
-            auto put_pair = [&](uint16_t* dst, const uint16_t* lo, const uint16_t* hi) {
-                for (int ch = 0; ch < 3; ++ch) { dst[2 * ch] = lo ? lo[ch] : 0; dst[2 * ch + 1] = hi ? hi[ch] : 0; }
-            };
-            uint16_t* A = rec.data();
-            uint16_t* B = rec.data() + kIcc16TableABytes / 2;
-            for (size_t r = 0; r < G; ++r)
-                for (size_t g = 0; g < G; ++g)
-                    for (size_t b = 0; b < G; ++b) {
-                        const size_t n_ = (r * G + g) * G + b;
-                        put_pair(A + 6 * n_, node_at(r, g, b), node_at(r + 1, g + 1, b + 1));
-                        put_pair(B + 6 * (3 * n_ + 0), node_at(r, g, b), node_at(r + 1, g, b));
-                        put_pair(B + 6 * (3 * n_ + 1), node_at(r, g, b), node_at(r, g + 1, b));
-                        put_pair(B + 6 * (3 * n_ + 2), node_at(r, g, b), node_at(r, g, b + 1));
-                    }
-        }
-#else
-        for (size_t r = 0; r < G; ++r)
-            for (size_t g = 0; g < G; ++g)
-                for (size_t b = 0; b < G; ++b) {
-                    uint16_t* dst = rec.data() + ((r * G + g) * G + b) * kRecU16;
-                    auto put = [&](int unit, int half, int j) {            // node of corner j -> its place in the unit
-                        const size_t rr = r + ((j >> 2) & 1), gg = g + ((j >> 1) & 1), bb = b + (j & 1);
-                        if (!(rr < G && gg < G && bb < G)) return;
-                        const uint16_t* node = t->table[(rr * G + gg) * G + bb];
-                        for (int ch = 0; ch < 3; ++ch) dst[(kIcc16UnitBytes / 2) * unit + 2 * ch + half] = node[ch];      // {a.R, b.R, a.G, b.G, a.B, b.B, 0, 0}
-                    };
-                    put(kIcc16BaseUnit, 0, 0); put(kIcc16BaseUnit, 1, 7);
-                    for (int idx = 0; idx < 8; ++idx) {
-                        const int amax = kIcc16AxesOfIdx[idx][0], amin = kIcc16AxesOfIdx[idx][1];
-                        if (amax < 0) continue;
-                        put(idx, 0, 4 >> amax); put(idx, 1, 7 - (4 >> amin));
-                    }
-                }
-#endif
-        e = hipDeviceSynchronize();                             // a launch may still be reading the previous table
-        if (e == hipSuccess) e = hipMemcpy(c.icc16, rec.data(), rec_bytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess) return hip_fail(e, "upload of the ICC table", AVIFGPU_writErr);
-        c.icc16_host.assign(reinterpret_cast<const uint8_t*>(t->table), reinterpret_cast<const uint8_t*>(t->table) + n);
-    }
-    c.icc16_src = t; c.icc16_fp = fp; c.icc16_epoch = epoch;
-    p.icc16_clut = static_cast<const uint16_t*>(c.icc16);
-    return 0;
-}
-
-int upload_icc_sampled(const avifgpu_icc_sampled32* t, WriteParams& p)
-{
-    // curve[] (768 KiB) followed by table16[] (24 KiB): one device buffer, one upload when the profile changes
-    const size_t nc = sizeof(t->curve), nt = sizeof(t->table16), n = nc + nt;
-    for (int ch = 0; ch < 3; ++ch)
-        if (t->entries[ch] < 0 || t->entries[ch] > AVIFGPU_ICC_SAMPLED_MAX || t->entries[ch] == 1)
-            return fail(AVIFGPU_formatBadParameters, "sampled ICC curves: entries[] must be 0 or 2..%d", (int)AVIFGPU_ICC_SAMPLED_MAX);
-    int dev = -1;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return hip_fail(e, "hipGetDevice", AVIFGPU_writErr);
-    std::lock_guard<std::mutex> lk(g_icc_mu);
-    IccDeviceTables& c = g_icc_tables[dev];
-    if (!c.s32) {
-        e = hipMalloc(&c.s32, n);
-        if (e != hipSuccess) { c.s32 = nullptr; return hip_fail(e, "hipMalloc(sampled ICC curves)", AVIFGPU_memFullErr); }
-    }
-    const uint8_t* host = reinterpret_cast<const uint8_t*>(t->curve);        // curve[] and table16[] are adjacent members
-    static_assert(offsetof(avifgpu_icc_sampled32, table16) == offsetof(avifgpu_icc_sampled32, curve) + sizeof(t->curve), "one span");
-    const uint64_t fp = table_fingerprint(host, n);
-    const uint64_t epoch = g_icc_epoch.load(std::memory_order_relaxed);
-    if (!(c.s32_epoch == epoch && c.s32_src == t && c.s32_fp == fp && c.s32_host.size() == n) && (c.s32_host.size() != n || memcmp(c.s32_host.data(), host, n) != 0)) {
-        e = hipDeviceSynchronize();                             // a launch may still be reading the previous curves
-        if (e == hipSuccess) e = hipMemcpy(c.s32, host, n, hipMemcpyHostToDevice);
-        if (e != hipSuccess) return hip_fail(e, "upload of the sampled ICC curves", AVIFGPU_writErr);
-        c.s32_host.assign(host, host + n);
-    }
-    c.s32_src = t; c.s32_fp = fp; c.s32_epoch = epoch;
-    p.icc_s_tab = static_cast<const float*>(c.s32);
-    p.icc_s_tab16 = reinterpret_cast<const uint16_t*>(static_cast<const uint8_t*>(c.s32) + nc);
-    // a mixed profile: the channels of parametric_mask carry a parametric curve (base.trc_type / trc_params), the others a table
-    if (t->parametric_mask < 0 || t->parametric_mask >= 7) return fail(AVIFGPU_formatBadParameters, "sampled ICC curves: parametric_mask must leave at least one sampled channel");
-    bool lds = !(g_hot_variant & 64);                           // bit 6: tests take the memory path
-    for (int ch = 0; ch < 3; ++ch) {
-        const bool par = (t->parametric_mask >> ch) & 1;
-        if (par && t->entries[ch] != 0) return fail(AVIFGPU_formatBadParameters, "sampled ICC curves: a parametric channel has no table entries");
-        if (par != (t->base.trc_type[ch] != 0)) return fail(AVIFGPU_formatBadParameters, "sampled ICC curves: parametric_mask and base.trc_type[] disagree");
-        lds = lds && (par || t->entries[ch] > 0);
-    }
-    for (int ch = 0; ch < 3; ++ch) p.icc_s_n[ch] = lds ? t->entries[ch] : 0;
-    p.icc_s_lds = lds;
-    p.icc_s_par = t->parametric_mask;
-    return 0;
-}
-
-int upload_icc8(const avifgpu_icc_shaper8* t, WriteParams& p)
-{
-    if (memcmp(t->shaper2[0], t->shaper2[1], 16385) != 0 || memcmp(t->shaper2[0], t->shaper2[2], 16385) != 0)
-        return fail(AVIFGPU_formatBadParameters, "8-bit ICC shaper: the destination curve must be the same for R, G and B (sRGB)");
-    // the kernel multiplies with v_mul_i32_i24: every factor must fit 24 signed bits (always true for real profiles: curve
-    // values <= 1.0 -> 16384, matrix coefficients of a few units)
-    for (int c = 0; c < 3; ++c) {
-        for (int i = 0; i < 256; ++i)
-            if (t->shaper1[c][i] < -(1 << 23) || t->shaper1[c][i] >= (1 << 23))
-                return fail(AVIFGPU_formatCannotRead, "8-bit ICC shaper: curve value out of the 24-bit range, keep the lcms2 path");
-        for (int j = 0; j < 3; ++j)
-            if (t->matrix[c][j] < -(1 << 23) || t->matrix[c][j] >= (1 << 23))
-                return fail(AVIFGPU_formatCannotRead, "8-bit ICC shaper: matrix coefficient out of the 24-bit range, keep the lcms2 path");
-    }
-    const size_t n1 = sizeof(t->shaper1), n2 = 16388;
-    std::vector<uint8_t> blob(n1 + n2);
-    memcpy(blob.data(), t->shaper1, n1);
-    memcpy(blob.data() + n1, t->shaper2[0], n2);
-    int dev = -1;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return hip_fail(e, "hipGetDevice", AVIFGPU_writErr);
-    std::lock_guard<std::mutex> lk(g_icc_mu);
-    IccDeviceTables& c = g_icc_tables[dev];
-    if (!c.icc8) {
-        e = hipMalloc(&c.icc8, n1 + n2);
-        if (e != hipSuccess) { c.icc8 = nullptr; return hip_fail(e, "hipMalloc(icc8 tables)", AVIFGPU_memFullErr); }
-    }
-    if (c.icc8_host != blob) {
-        e = hipDeviceSynchronize();
-        if (e == hipSuccess) e = hipMemcpy(c.icc8, blob.data(), blob.size(), hipMemcpyHostToDevice);
-        if (e != hipSuccess) return hip_fail(e, "upload of ICC tables", AVIFGPU_writErr);
-        c.icc8_host.swap(blob);
-    }
-    p.icc8_s1 = static_cast<const int32_t*>(c.icc8);
-    p.icc8_s2 = static_cast<const uint8_t*>(c.icc8) + n1;
-    for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) p.icc8_m[3 * i + j] = t->matrix[i][j]; p.icc8_off[i] = t->offset[i]; }
-    // the packed u8 kernel can take two of the three products of a matrix row in one v_dot2_i32_i16 when their operands fit 16
-    // signed bits: the G and B columns (a coefficient of 2.0 or more -- 32768 in 1.14 -- sits on the diagonal of a wide-gamut red,
-    // ProPhoto or ACES to sRGB, i.e. in column 0, which keeps its 24-bit multiply) and the G and B shaper tables (<= 16384 for curves into [0, 1])
-    bool fits = true;
-    for (int i = 0; i < 3; ++i) for (int j = 1; j < 3; ++j) fits = fits && t->matrix[i][j] >= -32768 && t->matrix[i][j] <= 32767;
-    for (int c2 = 1; c2 < 3; ++c2) for (int v = 0; v < 256; ++v) fits = fits && t->shaper1[c2][v] >= 0 && t->shaper1[c2][v] <= 32767;
-    p.icc8_dot2 = (fits && !(g_hot_variant & 32)) ? 1 : 0;  // bit 5 of the tuning word: tests take the three-mad form on the same data
-    for (int i = 0; i < 3; ++i) p.icc8_m12[i] = (int32_t)(((uint32_t)t->matrix[i][1] & 0xffffu) | ((uint32_t)t->matrix[i][2] << 16));
-    return 0;
-}
-
-// The stage program of a 32-bit document (icc = 8): its stage records, then its words (padded: the kernel copies whole dwords to LDS).  Small
-// -- a 17^3 program is ~36 KiB -- so every call compares the caller's program with the device copy outright and re-uploads on any difference:
-// a program rewritten at the same address between two saves is never served stale.
-int upload_icc_pipeline32(const avifgpu_icc_pipeline32* t, WriteParams& p)
-{
-    constexpr size_t kRecBytes = sizeof(avifgpu_icc_stage32) * AVIFGPU_ICC_PIPE_MAX_STAGES;
-    constexpr size_t kCap = kRecBytes + sizeof(t->words) + 16;
-    const size_t rec = sizeof(avifgpu_icc_stage32) * (size_t)t->stage_count, words = (size_t)t->word_count * 2;
-    std::vector<uint8_t> blob(kRecBytes + ((words + 15) & ~(size_t)15), 0);
-    memcpy(blob.data(), t->stages, rec);
-    memcpy(blob.data() + kRecBytes, t->words, words);
-    int dev = -1;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return hip_fail(e, "hipGetDevice", AVIFGPU_writErr);
-    std::lock_guard<std::mutex> lk(g_icc_mu);
-    IccDeviceTables& c = g_icc_tables[dev];
-    if (!c.p32) {
-        e = hipMalloc(&c.p32, kCap);
-        if (e != hipSuccess) { c.p32 = nullptr; return hip_fail(e, "hipMalloc(ICC stage program)", AVIFGPU_memFullErr); }
-    }
-    if (c.p32_host != blob) {
-        e = hipDeviceSynchronize();                             // a launch may still be reading the previous program
-        if (e == hipSuccess) e = hipMemcpy(c.p32, blob.data(), blob.size(), hipMemcpyHostToDevice);
-        if (e != hipSuccess) return hip_fail(e, "upload of the ICC stage program", AVIFGPU_writErr);
-        c.p32_host.swap(blob);
-    }
-    p.icc_p8_stages = c.p32;
-    p.icc_p8_words = reinterpret_cast<const uint16_t*>(static_cast<const uint8_t*>(c.p32) + kRecBytes);
-    p.icc_p8_nstages = t->stage_count;
-    p.icc_p8_lds_words = (words <= 48u * 1024u && !(g_hot_variant & 64)) ? t->word_count : 0;    // bit 6: tests take the memory path
-    for (int ch = 0; ch < 3; ++ch) p.icc_trc_type[ch] = 8;
-    return 0;
-}
-
 // avifgpu_shutdown: nothing is in flight any more.
 void release_device_caches()
 {
     release_read_tables();
-    std::lock_guard<std::mutex> lk(g_icc_mu);
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    for (auto& kv : g_icc_tables) {
-        (void)hipSetDevice(kv.first);
-        if (kv.second.icc8) (void)hipFree(kv.second.icc8);
-        if (kv.second.icc16) (void)hipFree(kv.second.icc16);
-        if (kv.second.pow_tab) (void)hipFree(kv.second.pow_tab);
-        if (kv.second.s32) (void)hipFree(kv.second.s32);
-        if (kv.second.p32) (void)hipFree(kv.second.p32);
-    }
-    g_icc_tables.clear();
-    if (cur >= 0) (void)hipSetDevice(cur);
-}
-
-// lcms2's parametric curve types 1..5 (DefaultEvalParametricFn; P = g, a, b, c, d, e, f as the library orders them) rewritten as
-//     y = R >= thr ? (a*R + b > 0 ? pow(a*R + b, g) + add : nonpos) : c*R + f
-// so that the kernel evaluates one branch-free expression.  Q = g, a, b, thr, c, f, add, nonpos.
-static void normalise_trc(int type, const double* P, double* Q)
-{
-    const double inf = std::numeric_limits<double>::infinity();
-    double g = P[0], a = 1, b = 0, thr = 0, c = 0, f = 0, add = 0, nonpos = 0;
-    switch (type) {
-    case 1:                                   // R < 0: R when |g - 1| < 1e-4, else 0;  R >= 0: pow(R, g)   (pow(0, g) = 0 = nonpos)
-        c = std::fabs(g - 1.0) < 0.0001 ? 1.0 : 0.0;
-        break;
-    case 2:                                   // |a| < 1e-4: 0;  R >= -b/a: (a*R + b > 0 ? pow : 0), else 0
-        if (std::fabs(P[1]) < 0.0001) { thr = inf; break; }
-        a = P[1]; b = P[2]; thr = -P[2] / P[1];
-        break;
-    case 3:                                   // as 2 with + c above and c below the (non-negative) break
-        if (std::fabs(P[1]) < 0.0001) { thr = inf; break; }
-        a = P[1]; b = P[2]; thr = std::max(-P[2] / P[1], 0.0); add = P[3]; f = P[3];
-        break;
-    case 4:                                   // R >= d: (a*R + b > 0 ? pow : 0), else c*R
-        a = P[1]; b = P[2]; thr = P[4]; c = P[3];
-        break;
-    default:                                  // 5: R >= d: (a*R + b > 0 ? pow + e : e), else c*R + f
-        a = P[1]; b = P[2]; thr = P[4]; c = P[3]; f = P[6]; add = P[5]; nonpos = P[5];
-        break;
-    }
-    Q[0] = g; Q[1] = a; Q[2] = b; Q[3] = thr; Q[4] = c; Q[5] = f; Q[6] = add; Q[7] = nonpos;
+    release_icc_tables();
 }
 
 int fill_write_params(const avifgpu_write_desc* d, int row0, int nrows, const WriteGeom& g, const IccArgs& icc, WriteParams& p)
 {
     memset(&p, 0, sizeof(p));
-    const avifgpu_icc_transform* g_icc = icc.s32 ? &icc.s32->base : icc.f32;
-    const avifgpu_icc_clut16* g_icc16 = icc.c16;
-    const avifgpu_icc_shaper8* g_icc8 = icc.s8;
-    if (icc.p32) {
-        if (d->depth != 32 || d->planes < 3) return fail(AVIFGPU_formatBadParameters, "the ICC stage program applies to 32-bit RGB(A) documents");
-        if (g_icc) return fail(AVIFGPU_formatBadParameters, "one ICC transform per call");
-        // the reference converts to sRGB only for the SDR save of a 32-bit document (ColorProfileConversion.cpp:118-123)
-        if (icc.p32->target == AVIFGPU_ICC_TARGET_SRGB_FLOAT && d->transfer != AVIFGPU_TRANSFER_CLIP)
-            return fail(AVIFGPU_formatBadParameters, "the sRGB ICC target goes with transfer Clip");
-        const int rc = upload_icc_pipeline32(icc.p32, p);
-        if (rc) return rc;
-    }
-    if (g_icc) {
-        if (d->depth != 32 || d->planes < 3) return fail(AVIFGPU_formatBadParameters, "the ICC row transform applies to 32-bit RGB(A) documents");
-        if (icc.s32) {
-            // sampled curves: the curve stage is the device table; the matrix / output curve below are shared with the parametric form
-            const int rc = upload_icc_sampled(icc.s32, p);
-            if (rc) return rc;
-        }
-        for (int c = 0; c < 3; ++c) {
-            if (icc.s32 && !((p.icc_s_par >> c) & 1)) { p.icc_trc_type[c] = 6; continue; }     // 6 marks "sampled" for the launchers
-            if (g_icc->trc_type[c] < 1 || g_icc->trc_type[c] > 5) return fail(AVIFGPU_formatBadParameters, "bad ICC curve type");
-            p.icc_trc_type[c] = g_icc->trc_type[c];
-            p.icc_trc_linear[c] = g_icc->trc_type[c] == 1 && g_icc->trc_params[c][0] == 1.0;
-            normalise_trc(g_icc->trc_type[c], g_icc->trc_params[c], p.icc_trc[c]);
-            const float gh = (float)p.icc_trc[c][0];
-            p.icc_trc_f[c][0] = gh; p.icc_trc_f[c][1] = (float)(p.icc_trc[c][0] - (double)gh);
-            for (int k = 1; k < 8; ++k) p.icc_trc_f[c][k + 1] = (float)p.icc_trc[c][k];
-        }
-        // One curve for R, G and B (what every matrix/TRC display profile with a parametric or gamma curve has) whose general form
-        //     y = R >= thr ? (a R + b > 0 ? pow(a R + b, g) + add : nonpos) : c R + f
-        // never takes the "a R + b <= 0" side with a value other than what pow(0, g) + add gives: a > 0, a thr + b >= 0 and
-        // nonpos == add, g > 0.  Then exp2(g log2(a R + b)) + add is the whole upper branch (log2 0 = -inf -> 0), and the streaming
-        // kernels evaluate the curve on the samples exactly as loaded (icc = 2 on write_rgb32_icc1_ycbcr444_hot and its siblings).
-        {
-            bool same = true;
-            for (int c = 1; c < 3; ++c)
-                for (int k = 0; k < 8; ++k) same = same && p.icc_trc[c][k] == p.icc_trc[0][k];
-            const double* Q = p.icc_trc[0];                    // g, a, b, thr, c, f, add, nonpos
-            const bool linear = p.icc_trc_linear[0] && p.icc_trc_linear[1] && p.icc_trc_linear[2];
-            // The kernels evaluate fmaf(a, R, b) with the FLOAT-rounded a, b and thr (icc_trc_f) and no "a R + b > 0" guard, so the
-            // qualification is made on those: fmaf is monotone in R for a > 0, hence fmaf(a, thr, b) >= 0 covers every R >= thr and the
-            // v_log_f32 never sees a negative number (a type-2/3 curve with b != 0 has thr = -b / a, where the rounded operands can land
-            // an ulp below zero: such a curve takes the generic kernel, which has the guard).
-            const float af = p.icc_trc_f[0][2], bf = p.icc_trc_f[0][3], thrf = p.icc_trc_f[0][4];
-            p.icc_same_simple = !icc.s32 && same && !linear && Q[0] > 0.0 && af > 0.0f && std::isfinite(Q[3]) && std::isfinite(thrf) &&
-                                Q[1] * Q[3] + Q[2] >= 0.0 && std::fmaf(af, thrf, bf) >= 0.0f && Q[7] == Q[6];
-        }
-        for (int k = 0; k < 9; ++k) { p.icc_m[k] = g_icc->matrix[k]; p.icc_m_f[k] = (float)g_icc->matrix[k]; }
-        { const int rc = upload_icc_pow_table(p); if (rc) return rc; }
-        if (g_icc->out_curve != 0) {
-            if (g_icc->out_curve != 4) return fail(AVIFGPU_formatBadParameters, "bad ICC output curve");
-            // the reference converts to sRGB only for the SDR save of a 32-bit document (ColorProfileConversion.cpp:118-123)
-            if (d->transfer != AVIFGPU_TRANSFER_CLIP) return fail(AVIFGPU_formatBadParameters, "the sRGB ICC target goes with transfer Clip");
-            p.icc_out = 4;
-            for (int k = 0; k < 8; ++k) p.icc_out_p[k] = g_icc->out_params[k];
-            p.icc_out_rcp[0] = std::fabs(g_icc->out_params[1]) < 0.0001 ? 0.0 : 1.0 / g_icc->out_params[1];
-            p.icc_out_rcp[1] = std::fabs(g_icc->out_params[3]) < 0.0001 ? 0.0 : 1.0 / g_icc->out_params[3];
-            const double ig = p.icc_out_p[6];                  // 1/g
-            const float ih = (float)ig;
-            p.icc_out_f[0] = ih; p.icc_out_f[1] = (float)(ig - (double)ih);
-            p.icc_out_f[2] = (float)p.icc_out_p[2];
-            p.icc_out_f[3] = (float)p.icc_out_rcp[0];
-            p.icc_out_f[4] = (float)p.icc_out_rcp[1];
-            p.icc_out_f[5] = (float)p.icc_out_p[5];
-            p.icc_out_f[6] = (std::fabs(p.icc_out_p[0]) < 0.0001 || std::fabs(p.icc_out_p[1]) < 0.0001) ? 0.0f : 1.0f;
-            p.icc_out_f[7] = std::fabs(p.icc_out_p[3]) < 0.0001 ? 0.0f : 1.0f;
-        }
-    }
-    if (g_icc16) {
-        if (d->depth != 16 || d->planes < 3) return fail(AVIFGPU_formatBadParameters, "the 16-bit ICC table applies to 16-bit RGB(A) documents");
-        const int rc = upload_icc16(g_icc16, p);
-        if (rc) return rc;
-    }
-    if (icc.c8t) {
-        if (d->depth != 8 || d->planes < 3) return fail(AVIFGPU_formatBadParameters, "the 8-bit ICC table applies to 8-bit RGB(A) documents");
-        if (g_icc8) return fail(AVIFGPU_formatBadParameters, "one ICC transform per call");
-        const int rc = upload_icc16(icc.c8t, p);            // the same 33^3 table, the same device layout; the kernel differs (icc = 7)
-        if (rc) return rc;
-    }
-    if (g_icc8) {
-        if (d->depth != 8 || d->planes < 3) return fail(AVIFGPU_formatBadParameters, "the 8-bit ICC shaper applies to 8-bit RGB(A) documents");
-        const int rc = upload_icc8(g_icc8, p);
-        if (rc) return rc;
-    }
+    if (const int rc = fill_icc_params(d, icc, p)) return rc;     // icc_tables.cpp: the ICC stage, its device tables included
     p.width = d->width; p.nrows = nrows; p.rows_to_end = d->height - row0;
     p.transfer = d->depth == 32 ? d->transfer : AVIFGPU_TRANSFER_CLIP;
     p.premultiply = d->alpha_state == AVIFGPU_ALPHA_PREMULTIPLIED;

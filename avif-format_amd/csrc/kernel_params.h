@@ -1,5 +1,5 @@
 // kernel_params.h -- POD argument blocks handed to the gfx950 kernels (by value, in SGPRs/kernarg).
-// Host-side validation and coefficient derivation live in avifgpu_api.hip; the kernels trust these.
+// Host-side validation and coefficient derivation live in avifgpu_api.hip and icc_tables.cpp; the kernels trust these.
 #pragma once
 #include <stdint.h>
 
@@ -32,7 +32,7 @@ enum : int { kHotDefault = 1 | 2 | 4 };
 #endif
 constexpr bool span_load_cached(int k, int K) { return AG_EDGE_CACHED == 1 ? (k == 0 || k == K - 1) : ((AG_EDGE_CACHED >> (k + 4)) & 1) != 0; }
 
-// 16-bit ICC table on the device (upload_icc16 builds it, icc16_tetrahedral_host reads it): AG_ICC16_DOT2 picks the layout.  Both keep
+// 16-bit ICC table on the device (icc16_device_image, icc_tables.h, builds it; icc16_tetrahedral_host reads it): AG_ICC16_DOT2 picks the layout.  Both keep
 // node PAIRS per channel (lo | hi << 16), the operand form of v_dot2_u32_u16, and cost a pixel two 12-byte gathers.
 //   2 (default)  node-pair tables, 1.76 MB, L2-resident
 //   1            one 128-byte record per cell (every node stored up to eight times, 4.6 MB): 1 % faster on photograph-like input, but
@@ -79,7 +79,7 @@ struct WriteParams {
     int32_t icc_trc_type[3];     // lcms2 parametric type per channel (0 = no ICC stage)
     int32_t icc_out;             // 0 | 4: output curve after the matrix (avifgpu_icc_transform::out_curve)
     int32_t icc_trc_linear[3];   // channel curve is gamma 1 (identity on every float)
-    int32_t icc_same_simple;     // all three channel curves are the SAME parametric curve in its "simple" form (fill_write_params): the
+    int32_t icc_same_simple;     // all three channel curves are the SAME parametric curve in its "simple" form (fill_icc_params): the
                                  // streaming kernels evaluate it per sample as loaded, R >= thr ? exp2(g log2(a R + b)) + add : c R + f
     double  icc_trc[3][8];       // normalised: g, a, b, thr, c, f, add, nonpos (see icc_trc in write_kernels.hip)
     double  icc_m[9];
@@ -90,7 +90,7 @@ struct WriteParams {
     float   icc_out_f[9];        // (1/g)h, (1/g)l, b, 1/a, 1/c, break point, [g,a usable], [c usable], 0
     float   icc_m_f[9];          // the matrix rounded to float (single-precision variant 2)
     float   icc_pad_f[1];
-    const float* icc_pow_tab;    // 128 x {c, Lh, Ll, 0}: the bins of icc_pow32, built once per device on the host (upload_icc_pow_table)
+    const float* icc_pow_tab;    // 128 x {c, Lh, Ll, 0}: the bins of icc_pow32, built once on the host (icc_pow_bins, icc_tables.cpp)
     // 8-bit matrix-shaper transform (avifgpu_icc_shaper8): tables live in device memory, matrix in kernarg
     const int32_t* icc8_s1;      // [3][256] 1.14 fixed
     const uint8_t* icc8_s2;      // [16385] 8-bit output curve (identical for R,G,B: the destination is sRGB)

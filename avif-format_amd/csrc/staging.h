@@ -1,5 +1,6 @@
 // staging.h -- internal C++ interface between the host-side translation units of libavifgpu.so:
-//   avifgpu_api.hip  validation, descriptor -> kernel parameters, per-device table caches, the extern "C" entry points
+//   avifgpu_api.hip  validation, descriptor -> kernel parameters, the extern "C" entry points
+//   icc_tables.cpp   the ICC stage of a save: its kernel parameters, the per-device cache of its tables
 //   pipeline.hip     the bound device contexts: one worker thread + N staging slots per context; row-tile scheduler
 //   host_shim.cpp    the FormatRecord tile protocol above them
 //   staged_open.cpp  the entry checks and the staged host path of the oriented, upsampled and cropped opens
@@ -152,11 +153,11 @@ hipError_t launch_read(const ReadParams& p, int colorspace, int depth, bool alph
                        hipStream_t st, char* label);
 void release_device_caches();                        // read tables + ICC tables of every device (avifgpu_shutdown)
 
-// Device copies of the ICC tables, cached per HIP device, re-uploaded only when the contents change.
-int  upload_icc8(const avifgpu_icc_shaper8* t, WriteParams& p);
-void icc_epoch_for_call(int row0, int nrows);                                  // one call per C-ABI write call / shim tile that carries an ICC table (see IccDeviceTables)
-int  upload_icc16(const avifgpu_icc_clut16* t, WriteParams& p);
-int  upload_icc_sampled(const avifgpu_icc_sampled32* t, WriteParams& p);
+// ---- icc_tables.cpp: the ICC stage of a write call -- its WriteParams fields and the device copies of its tables, cached per HIP device
+// (the calling thread's current one) and re-uploaded only when the contents change -------------------------------------
+int  fill_icc_params(const avifgpu_write_desc* d, const IccArgs& icc, WriteParams& p);     // p zeroed; the first half of fill_write_params
+void icc_epoch_for_call(int row0, int nrows);        // one call per C-ABI write call / shim tile that carries an ICC table (IccVerify, icc_tables.h)
+void release_icc_tables();                           // every device's, under hipSetDevice; the caller's device is restored
 
 // ---- pipeline.hip: bound contexts, staging slots, the row-tile scheduler --------------------------------------------
 // A context = one HIP device ordinal + one worker thread + kSlots staging slots (device in/out buffers, pinned host in/out
