@@ -38,6 +38,8 @@ CHROMA_ZERO_LIBHEIF, CHROMA_ZERO_DECODER = 0, 1
 PQ_AUTO, PQ_COMPACT, PQ_CLOSE = 0, 1, 2
 MEM_HOST, MEM_DEVICE = 0, 1
 UPSAMPLE_NEAREST, UPSAMPLE_BILINEAR_CENTER, UPSAMPLE_BILINEAR_LEFT = 0, 1, 2
+# AVIFGPU_ICC_KIND_*: which prepared structure the icc argument of avifgpu_write_rows_grid points to
+ICC_KIND_NONE, ICC_KIND_TRANSFORM, ICC_KIND_SAMPLED, ICC_KIND_SHAPER8, ICC_KIND_CLUT16, ICC_KIND_CLUT8_TABLE, ICC_KIND_PIPELINE32 = range(7)
 
 noErr, userCanceledErr, readErr, writErr, memFullErr = 0, -128, -19, -20, -108
 formatBadParameters, formatCannotRead = -30500, -30501
@@ -293,6 +295,14 @@ ABI = [
                                          c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p]),
     ("avifgpu_probe_grid_gather", c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                             c_void_p, c_int64, c_void_p]),
+    ("avifgpu_write_grid_check", c_int32, [POINTER(WriteDesc), POINTER(Grid)]),
+    ("avifgpu_write_grid_scratch_bytes", c_int64, [POINTER(WriteDesc), c_int32]),
+    ("avifgpu_grid_fit", c_int32, [POINTER(WriteDesc), c_int32, c_int32, c_int32, POINTER(Grid)]),
+    ("avifgpu_grid_payload", c_int32, [POINTER(Grid), c_int32, c_int32, c_void_p, c_int64]),
+    ("avifgpu_write_rows_grid", c_int32, [POINTER(WriteDesc), c_int32, c_void_p, POINTER(Grid), c_void_p, c_int32, c_int32, c_void_p, c_int64,
+                                          c_void_p, c_int64, c_int32, c_void_p]),
+    ("avifgpu_probe_grid_scatter", c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                             c_void_p, c_int64, c_void_p]),
 ]
 
 
@@ -316,7 +326,9 @@ ABI4_NEW = frozenset(("avifgpu_probe_pattern_read", "avifgpu_probe_pattern_rgb32
                       "avifgpu_read_cropped_scratch_bytes", "avifgpu_read_rows_cropped", "avifgpu_probe_crop",
                       "avifgpu_host_read_heif_image_cropped",   # (the cropped open)
                       "avifgpu_grid_parse", "avifgpu_grid_check", "avifgpu_read_grid_scratch_bytes", "avifgpu_read_rows_grid",
-                      "avifgpu_probe_grid_gather", "avifgpu_host_read_heif_image_grid"))   # (the grid open)
+                      "avifgpu_probe_grid_gather", "avifgpu_host_read_heif_image_grid",   # (the grid open)
+                      "avifgpu_write_grid_check", "avifgpu_write_grid_scratch_bytes", "avifgpu_grid_fit", "avifgpu_grid_payload",
+                      "avifgpu_write_rows_grid", "avifgpu_probe_grid_scatter", "avifgpu_host_create_heif_image_grid"))   # (the grid save)
 
 
 def bind(lib: ctypes.CDLL, table=ABI) -> ctypes.CDLL:
@@ -496,6 +508,20 @@ class AvifGpu:
     def probe_grid_gather(self, tiles_dev, columns, plane, tile_w, tile_h, bytes_per_sample, x0, y0, w, h, dst, dst_row_bytes, stream=None):
         """Launch the grid gather kernel alone on one plane (avifgpu_probe_grid_gather)."""
         self._check(self.lib.avifgpu_probe_grid_gather(tiles_dev, columns, plane, tile_w, tile_h, bytes_per_sample, x0, y0, w, h, dst, dst_row_bytes, stream))
+
+    def write_rows_grid(self, desc: WriteDesc, grid, tiles, row0, nrows, src_ptr, src_row_bytes, scratch_ptr=None, scratch_bytes=0,
+                        mem=MEM_DEVICE, stream=0, icc=None):
+        """Save rows [row0, row0 + nrows) into the padded tiles of a grid (avifgpu_write_rows_grid): tiles is the address of columns * rows
+        GridTile records where `mem` says (or a ctypes array of them for MEM_HOST); icc: a prepared ICC structure or None."""
+        if isinstance(tiles, ctypes.Array):
+            tiles = ctypes.addressof(tiles)
+        self._check(self.lib.avifgpu_write_rows_grid(ctypes.byref(desc), icc_kind_of(icc, desc), ctypes.byref(icc) if icc is not None else None,
+                                                     ctypes.byref(grid_of(grid)), tiles or None, row0, nrows, src_ptr, src_row_bytes,
+                                                     scratch_ptr or None, scratch_bytes, mem, stream or None))
+
+    def probe_grid_scatter(self, tiles_dev, columns, plane, tile_w, tile_h, bytes_per_pixel, plane_w, plane_h, y0, h, src, src_row_bytes, stream=None):
+        """Launch the grid scatter kernel alone on one plane (avifgpu_probe_grid_scatter)."""
+        self._check(self.lib.avifgpu_probe_grid_scatter(tiles_dev, columns, plane, tile_w, tile_h, bytes_per_pixel, plane_w, plane_h, y0, h, src, src_row_bytes, stream))
 
     def probe_crop(self, src, src_row_bytes, dst, dst_row_bytes, row_payload_bytes, rows, stream=None):
         """Launch the crop mover kernel alone on device buffers (avifgpu_probe_crop)."""
@@ -819,6 +845,42 @@ def read_grid_scratch_bytes(desc: ReadDesc, grid, rect, upsampling: int, orienta
     """Device scratch of a MEM_DEVICE call of onrows output rows of the grid open (avifgpu_read_grid_scratch_bytes)."""
     return _oserr(load().avifgpu_read_grid_scratch_bytes(ctypes.byref(desc), ctypes.byref(grid_of(grid)),
                                                           ctypes.byref(crop_rect(rect)) if rect is not None else None, upsampling, orientation, onrows))
+
+
+def write_grid_check(desc: WriteDesc, grid) -> None:
+    """Raise unless (desc, grid) is what the grid save takes (avifgpu_write_grid_check)."""
+    _oserr(load().avifgpu_write_grid_check(ctypes.byref(desc), ctypes.byref(grid_of(grid))))
+
+
+def write_grid_scratch_bytes(desc: WriteDesc, nrows: int) -> int:
+    """Device scratch of a MEM_DEVICE call of nrows rows of the grid save (avifgpu_write_grid_scratch_bytes)."""
+    return _oserr(load().avifgpu_write_grid_scratch_bytes(ctypes.byref(desc), nrows))
+
+
+def grid_fit(desc: WriteDesc, max_tile_width: int, max_tile_height: int, align: int = 1) -> tuple:
+    """(columns, rows, tile_width, tile_height) of the grid with the fewest tiles within the caps (avifgpu_grid_fit)."""
+    g = Grid()
+    _oserr(load().avifgpu_grid_fit(ctypes.byref(desc), max_tile_width, max_tile_height, align, ctypes.byref(g)))
+    return g.columns, g.rows, g.tile_width, g.tile_height
+
+
+def grid_payload(grid, width: int, height: int, capacity: int = 12) -> bytes:
+    """The ImageGrid item payload of (grid, width x height) (avifgpu_grid_payload)."""
+    buf = ctypes.create_string_buffer(max(capacity, 1))
+    n = _oserr(load().avifgpu_grid_payload(ctypes.byref(grid_of(grid)), width, height, ctypes.addressof(buf), capacity))
+    return buf.raw[:n]
+
+
+def icc_kind_of(icc, desc: WriteDesc) -> int:
+    """The AVIFGPU_ICC_KIND_* value that names the prepared structure `icc` for avifgpu_write_rows_grid."""
+    if icc is None:
+        return ICC_KIND_NONE
+    if isinstance(icc, IccClut16):
+        return ICC_KIND_CLUT8_TABLE if desc.depth == 8 else ICC_KIND_CLUT16
+    for cls, kind in ((IccPipeline32, ICC_KIND_PIPELINE32), (IccSampled32, ICC_KIND_SAMPLED), (IccShaper8, ICC_KIND_SHAPER8), (IccTransform, ICC_KIND_TRANSFORM)):
+        if isinstance(icc, cls):
+            return kind
+    raise TypeError("not a prepared ICC structure: %r" % (icc,))
 
 
 def read_oriented_scratch_bytes(desc: ReadDesc, orientation: int, onrows: int) -> int:

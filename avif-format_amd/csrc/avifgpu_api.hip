@@ -396,6 +396,14 @@ int write_rows_any(const avifgpu_write_desc* d, const IccArgs& icc, int32_t row0
 
 } // namespace
 
+namespace avifgpu {
+int write_rows_with_icc(const avifgpu_write_desc* d, const IccArgs& icc, int32_t row0, int32_t nrows, const void* src, int64_t src_row_bytes,
+                        void* const dst[4], const int64_t dst_stride[4], int32_t mem_kind, void* stream)
+{
+    return write_rows_any(d, icc, row0, nrows, src, src_row_bytes, dst, dst_stride, mem_kind, stream);
+}
+} // namespace avifgpu
+
 // ======================================================================================================
 extern "C" {
 

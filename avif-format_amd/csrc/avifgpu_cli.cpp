@@ -55,13 +55,13 @@ struct Args {
         "usage: avifgpu_cli write --width W --height H --depth 8|16|32 --planes 1..4 --bits 8|10|12 [--transfer clip|pq|smpte428]\n"
         "                         [--peak NITS] [--alpha none|straight|premultiplied] [--ycbcr 444|422|420] [--matrix N] [--primaries N]\n"
         "                         [--lossless] [--icc PROFILE [--keep-profile]] [--maxdata BYTES] [--device N]\n"
-        "                         [--light-level [--percentile P]] [--thumbnail BBOX THUMB.planes] [--summary] IN.raw OUT.planes\n"
+        "                         [--light-level [--percentile P]] [--thumbnail BBOX THUMB.planes] [--summary] [--grid COLSxROWS,TWxTH] IN.raw OUT.planes\n"
         "       avifgpu_cli read  --width W --height H --depth 8|16|32 --bits 8|10|12 --colorspace ycbcr|rgb|mono [--chroma 444|422|420]\n"
         "                         [--alpha none|straight|premultiplied] [--matrix N --primaries N --tc N [--limited]] [--peak NITS]\n"
         "                         [--hlg-ootf --gamma G] [--orientation 1..8] [--chroma-upsampling nearest|bilinear|bilinear-left]\n"
         "                         [--crop X0,Y0,W,H] [--grid COLSxROWS,TWxTH] [--maxdata BYTES] [--device N] IN.planes OUT.raw\n"
         "       --grid: IN.planes holds the tiles' planes, tile after tile in row-major order, each laid out like a whole image of TW x TH;\n"
-        "               --width / --height are the canvas\n");
+        "               --width / --height are the canvas.  write --grid saves into padded tiles and writes OUT.planes.tile0, .tile1, ... in that layout\n");
     exit(2);
 }
 
@@ -226,13 +226,41 @@ int do_write(const Args& a)
         if (src) return fail("avifgpu_summary_attach", src);
     }
     avifgpu_image img{};
-    const int rc = avifgpu_host_create_heif_image(&g_host.fr, a.alpha, &o, a.output, a.lossless ? AVIFGPU_MATRIX_RGB_GBR : a.matrix,
-                                                  a.primaries, &img);
+    // --grid: the save goes straight into columns * rows padded tile images (avifgpu_host_create_heif_image_grid), one output file per tile
+    std::vector<avifgpu_image> tiles;
+    const avifgpu_grid grid = { a.grid_cols, a.grid_rows, a.grid_tw, a.grid_th };
+    if (a.grid) {
+        if (a.grid_cols < 1 || a.grid_cols > 256 || a.grid_rows < 1 || a.grid_rows > 256 || a.grid_tw < 1 || a.grid_th < 1) { fprintf(stderr, "avifgpu_cli: bad --grid\n"); return 2; }
+        tiles.assign((size_t)a.grid_cols * a.grid_rows, avifgpu_image{});
+    }
+    const int matrix = a.lossless ? AVIFGPU_MATRIX_RGB_GBR : a.matrix;
+    const int rc = a.grid ? avifgpu_host_create_heif_image_grid(&g_host.fr, a.alpha, &o, a.output, matrix, a.primaries, &grid, tiles.data())
+                          : avifgpu_host_create_heif_image(&g_host.fr, a.alpha, &o, a.output, matrix, a.primaries, &img);
     fclose(g_host.file);
     if (a.light_level) (void)avifgpu_histogram_attach(nullptr, 0, AVIFGPU_MEM_HOST);
     if (a.thumb_bbox) (void)avifgpu_thumbnail_attach(nullptr, 0, 0, AVIFGPU_MEM_HOST);
     if (a.summary) (void)avifgpu_summary_attach(nullptr, AVIFGPU_MEM_HOST);
-    if (rc) return fail("avifgpu_host_create_heif_image", rc);
+    if (rc) { for (avifgpu_image& t : tiles) avifgpu_image_free(&t); return fail(a.grid ? "avifgpu_host_create_heif_image_grid" : "avifgpu_host_create_heif_image", rc); }
+    if (a.grid) {
+        // OUT.tile<k>: the planes of tile k in order 0..3, tight rows -- the layout `read --grid` takes tile after tile
+        size_t total = 0;
+        for (size_t k = 0; k < tiles.size(); ++k) {
+            const std::string name = a.out + ".tile" + std::to_string(k);
+            FILE* out = fopen(name.c_str(), "wb");
+            if (!out) { perror(name.c_str()); for (avifgpu_image& t : tiles) avifgpu_image_free(&t); return 1; }
+            for (int pl = 0; pl < 4; ++pl) {
+                if (!tiles[k].plane[pl]) continue;
+                const size_t rb = plane_row_bytes(tiles[k], pl);
+                for (int y = 0; y < plane_rows(tiles[k], pl); ++y) total += fwrite(tiles[k].plane[pl] + (size_t)y * tiles[k].stride[pl], 1, rb, out);
+            }
+            fclose(out);
+        }
+        uint8_t payload[12];
+        const int np = avifgpu_grid_payload(&grid, a.width, a.height, payload, sizeof payload);
+        fprintf(stderr, "write: %dx%d depth %d -> %d-bit, %d x %d tiles of %d x %d, %d requests, %zu bytes, ImageGrid payload of %d bytes\n", a.width, a.height, a.depth, a.bits,
+                a.grid_cols, a.grid_rows, a.grid_tw, a.grid_th, g_host.tiles, total, np);
+        for (avifgpu_image& t : tiles) avifgpu_image_free(&t);
+    }
     if (a.summary) {
         avifgpu_save_summary sm{};
         const int src = avifgpu_summary_read(&td, counters, &sm);
@@ -269,6 +297,7 @@ int do_write(const Args& a)
         fprintf(stderr, "light-level: MaxCLL %u MaxFALL %u code %d pixels %llu\n", (unsigned)ll.max_cll, (unsigned)ll.max_fall, (int)ll.max_code,
                 (unsigned long long)ll.pixels);
     }
+    if (a.grid) return 0;
     FILE* out = fopen(a.out.c_str(), "wb");
     if (!out) { perror(a.out.c_str()); return 1; }
     size_t total = 0;

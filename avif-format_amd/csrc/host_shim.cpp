@@ -25,6 +25,7 @@
 
 #include "../../include/avifgpu_host.h"
 #include "staging.h"
+#include "grid_save.h"
 
 namespace avifgpu::host {
 
@@ -119,7 +120,8 @@ struct WritePlan { avifgpu_write_desc desc; int output; };
 // the tile loop that replaces WriteHeifImage.cpp:1017-1135 (and its five siblings).
 void CreateHeifImageInto(FormatRecordPtr formatRecord, AlphaState alphaState, const VPoint& imageSize,
                          const SaveUIOptions& callerOptions, int output, int matrix, int primaries, avifgpu_image* img,
-                         const avifgpu_icc_clut16* documentToSRGB16 = nullptr, const avifgpu_icc_pipeline32* documentPipeline = nullptr)
+                         const avifgpu_icc_clut16* documentToSRGB16 = nullptr, const avifgpu_icc_pipeline32* documentPipeline = nullptr,
+                         const avifgpu_grid* grid = nullptr, avifgpu_image* gridTiles = nullptr)   // a grid save: img is null, the planes go to columns * rows tile images
 {
     const bool hasAlpha = alphaState != AlphaState::None;
     const bool mono = IsMonochromeImage(formatRecord);
@@ -167,16 +169,40 @@ void CreateHeifImageInto(FormatRecordPtr formatRecord, AlphaState alphaState, co
     if (mono) d.output = AVIFGPU_OUT_REFERENCE;
 
     // describe the image the way CreateHeifImage / heif_image_add_plane do (WriteHeifImage.cpp:31-39,:63-85,:181-194)
-    img->width = d.width; img->height = d.height; img->bit_depth = d.bit_depth;
-    img->has_alpha = hasAlpha;
-    img->premultiplied_alpha = alphaState == AlphaState::Premultiplied;
-    if (output == AVIFGPU_OUT_YCBCR && !mono) { img->colorspace = AVIFGPU_COLORSPACE_YCBCR; img->chroma = d.chroma; }
-    else if (mono) { img->colorspace = AVIFGPU_COLORSPACE_MONOCHROME; img->chroma = AVIFGPU_CHROMA_MONOCHROME; }
-    else {
-        img->colorspace = AVIFGPU_COLORSPACE_RGB;
-        img->chroma = d.bit_depth == 8 ? (hasAlpha ? 11 : 10) : (hasAlpha ? 15 : 14);   // interleaved RGB(A) / RRGGBB(AA)_LE
-    }
-    if (!img->plane[0]) OSErrException::ThrowIfError(avifgpu_image_alloc(img));
+    auto describe = [&](avifgpu_image* img, int width, int height) {
+        img->width = width; img->height = height; img->bit_depth = d.bit_depth;
+        img->has_alpha = hasAlpha;
+        img->premultiplied_alpha = alphaState == AlphaState::Premultiplied;
+        if (output == AVIFGPU_OUT_YCBCR && !mono) { img->colorspace = AVIFGPU_COLORSPACE_YCBCR; img->chroma = d.chroma; }
+        else if (mono) { img->colorspace = AVIFGPU_COLORSPACE_MONOCHROME; img->chroma = AVIFGPU_CHROMA_MONOCHROME; }
+        else {
+            img->colorspace = AVIFGPU_COLORSPACE_RGB;
+            img->chroma = d.bit_depth == 8 ? (hasAlpha ? 11 : 10) : (hasAlpha ? 15 : 14);   // interleaved RGB(A) / RRGGBB(AA)_LE
+        }
+        if (!img->plane[0]) OSErrException::ThrowIfError(avifgpu_image_alloc(img));
+    };
+    // a grid save: every tile is an image of tile_width x tile_height of the same kind, and their planes are the destination
+    std::vector<avifgpu_grid_tile> tileTable;
+    avifgpu::GridDest gridDest = {};
+    if (grid) {
+        avifgpu::WriteGeom wg;
+        const int gerr = avifgpu::check_write(&d, 0, 0, wg);
+        if (gerr) throw OSErrException((OSErr)gerr);
+        if (const char* why = avifgpu::grid_save_illegal(d.width, d.height, wg.xs, wg.ys, *grid)) {
+            avifgpu::fail(AVIFGPU_formatBadParameters, "avifgpu_host_create_heif_image_grid: %d x %d tiles of %d x %d for a %d x %d canvas: %s",
+                          grid->columns, grid->rows, grid->tile_width, grid->tile_height, d.width, d.height, why);
+            throw OSErrException(AVIFGPU_formatBadParameters);
+        }
+        tileTable.resize((size_t)grid->columns * grid->rows);
+        for (size_t k = 0; k < tileTable.size(); ++k) {
+            describe(&gridTiles[k], grid->tile_width, grid->tile_height);
+            for (int pl = 0; pl < 4; ++pl) { tileTable[k].plane[pl] = gridTiles[k].plane[pl]; tileTable[k].stride[pl] = gridTiles[k].stride[pl]; }
+        }
+        // preset planes are the caller's: a NULL pointer or a short stride is refused here, before the host is asked for a row
+        if (const int terr = avifgpu::check_grid_tiles(&d, wg, *grid, tileTable.data(), "avifgpu_host_create_heif_image_grid")) throw OSErrException((OSErr)terr);
+        gridDest.grid = *grid; gridDest.tiles = tileTable.data();
+        img = &gridTiles[0];                                     // the kind of every tile, for what follows
+    } else describe(img, d.width, d.height);
 
     // ICC row transform (replaces converter.ConvertRow, WriteHeifImage.cpp:1012,1031-1034) for the HDR case
     avifgpu_icc_transform icc;
@@ -280,8 +306,8 @@ void CreateHeifImageInto(FormatRecordPtr formatRecord, AlphaState alphaState, co
         // NOTE: ColorProfileConversion::ConvertRow (lcms2, WriteHeifImage.cpp:1031-1034) is the caller's hook: it is
         // a no-op unless an ICC transform exists; INTEGRATION.md shows where the plug-in keeps calling it per row.
 
-        void* dst[4]; int64_t stride[4];
-        for (int pl = 0; pl < 4; ++pl) {
+        void* dst[4] = {}; int64_t stride[4] = {};
+        for (int pl = 0; pl < 4 && !grid; ++pl) {                   // a grid save: the tiles are the destination, dst is not looked at
             const bool chromaPlane = img->colorspace == AVIFGPU_COLORSPACE_YCBCR && (pl == 1 || pl == 2);
             const int r = chromaPlane ? (top >> ys) : top;
             dst[pl] = img->plane[pl] ? img->plane[pl] + (int64_t)r * img->stride[pl] : nullptr;
@@ -290,7 +316,7 @@ void CreateHeifImageInto(FormatRecordPtr formatRecord, AlphaState alphaState, co
         // (the shim queues tiles itself, past avifgpu_write_rows: it advances the ICC table epoch the way that entry does -- the rows of a
         //  save ascend without a gap, so the first tile of every save starts a new epoch and each device re-verifies its copy of the table once per save)
         if (iccArgs.c16 || iccArgs.s32 || iccArgs.c8t) avifgpu::icc_epoch_for_call(top, bottom - top);
-        const int err = avifgpu::write_tile_enqueue(ctx, slot, &d, top, bottom - top, tile, formatRecord->rowBytes, dst, stride, iccArgs);
+        const int err = avifgpu::write_tile_enqueue(ctx, slot, &d, top, bottom - top, tile, formatRecord->rowBytes, dst, stride, iccArgs, grid ? &gridDest : nullptr);
         if (err) bail((OSErr)err);
     }
     formatRecord->data = nullptr;
@@ -623,9 +649,9 @@ avifgpu_OSErr avifgpu_host_create_heif_image(avifgpu_FormatRecord* formatRecord,
 static avifgpu_OSErr create_heif_image(avifgpu_FormatRecord* formatRecord, int32_t alphaState, const avifgpu_SaveUIOptions* saveOptions,
                                        int32_t output, int32_t matrix_coefficients, int32_t color_primaries,
                                        const avifgpu_icc_clut16* documentToSRGB16, const avifgpu_icc_pipeline32* documentPipeline,
-                                       avifgpu_image* img)
+                                       avifgpu_image* img, const avifgpu_grid* grid = nullptr, avifgpu_image* gridTiles = nullptr)
 {
-    if (!formatRecord || !saveOptions || !img || !formatRecord->advanceState) return AVIFGPU_formatBadParameters;
+    if (!formatRecord || !saveOptions || !(grid ? gridTiles : img) || !formatRecord->advanceState) return AVIFGPU_formatBadParameters;
     if (matrix_coefficients < 0) {                          // "what the plug-in will attach"
         avifgpu_nclx nclx;
         const avifgpu_OSErr e = avifgpu_host_save_nclx(formatRecord, saveOptions, &nclx);
@@ -640,8 +666,17 @@ static avifgpu_OSErr create_heif_image(avifgpu_FormatRecord* formatRecord, int32
         default: throw OSErrException(AVIFGPU_formatBadParameters);
         }
         CreateHeifImageInto(formatRecord, (AlphaState)alphaState, imageSize, *saveOptions, output, matrix_coefficients,
-                            color_primaries, img, documentToSRGB16, documentPipeline);
+                            color_primaries, img, documentToSRGB16, documentPipeline, grid, gridTiles);
     }, AVIFGPU_writErr);
+}
+
+avifgpu_OSErr avifgpu_host_create_heif_image_grid(avifgpu_FormatRecord* formatRecord, int32_t alphaState,
+                                                  const avifgpu_SaveUIOptions* saveOptions, int32_t output,
+                                                  int32_t matrix_coefficients, int32_t color_primaries,
+                                                  const avifgpu_grid* grid, avifgpu_image* tiles)
+{
+    if (!grid || !tiles) return AVIFGPU_formatBadParameters;
+    return create_heif_image(formatRecord, alphaState, saveOptions, output, matrix_coefficients, color_primaries, nullptr, nullptr, nullptr, grid, tiles);
 }
 
 avifgpu_OSErr avifgpu_host_create_heif_image_with_table(avifgpu_FormatRecord* formatRecord, int32_t alphaState,

@@ -32,12 +32,14 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include <pthread.h>
 #include <sched.h>
 
 #include "staging.h"
+#include "grid_save.h"
 
 namespace avifgpu {
 namespace {
@@ -63,8 +65,9 @@ struct Job {
     IccArgs icc;
     SaveStats stats;                                       // write: what the calling thread had armed (the enqueue side decides, the worker counts into its context's accumulators)
     // filled by start(): what finish() still has to copy out of the pinned bounce buffer
-    struct Bounce { uint8_t* dst; int64_t dst_stride; size_t off, pitch, bytes; int rows; } bounce[4];
-    int nbounce = 0;
+    struct Bounce { uint8_t* dst; int64_t dst_stride; size_t off, pitch, bytes; int rows; };
+    std::vector<Bounce> bounce;                            // one per pageable plane; a grid save: one per pageable tile piece
+    bool to_grid = false; GridDest grid{};                 // write: the planes go to the padded tiles of a grid save (staging.h)
     char label[kLabelBytes] = "";
     double t_queued = 0, t_start = 0, t_issued = 0;        // AVIFGPU_TRACE
     uint64_t upload_seq = 0;                               // position in its device's upload order (enqueue())
@@ -143,6 +146,9 @@ struct Ctx {
     // summed for, thumb_tw x thumb_th (touched by the thumbnail rows of each tile: only they travel back); AVIFGPU_SUMMARY_COUNTERS 32-bit maxima
     DeviceAccum hist, thumb, summary;
     int thumb_tw = 0, thumb_th = 0;
+    // a grid save: is the tile plane that starts here page-locked (all of it)?  Filled by the worker as it starts tiles, emptied by
+    // wait_all() -- the caller may unlock its memory between two calls; guarded like the accumulators above
+    std::unordered_map<const void*, bool> pinned_tiles;
 };
 constexpr size_t kHistBytes = 4096 * sizeof(uint64_t), kSummaryBytes = AVIFGPU_SUMMARY_COUNTERS * sizeof(uint32_t);
 
@@ -472,6 +478,61 @@ void forget_uploads_of(int device, const Slot& sl)
 }
 
 // ---- worker side -------------------------------------------------------------------------------------------------------
+// A grid save's way down, behind the tile's launch_write() on the slot's stream: grid_pad fills the pad columns and pad rows of the slot's
+// planes in place (they were allocated with the padded pitch and the pad rows), then the band of every plane goes down as ONE strided copy
+// per tile piece (grid_save_pieces) -- straight into page-locked tiles; a plane with a pageable piece also goes to the pinned bounce buffer
+// as a whole and the worker's copy lands those pieces in finish().  Returns an OSErr; the caller drains the stream.
+int grid_planes_down(Ctx& c, Job& j, Slot& sl, const WriteGeom& g, const GridSavePlane gp[4], const size_t off[4], const size_t pitch[4], size_t out_total)
+{
+    const avifgpu_write_desc* d = &j.wd;
+    hipStream_t st = sl.stream;
+    uint8_t* base[4] = {}; int64_t pit[4] = {};
+    for (int pl = 0; pl < 4; ++pl) {
+        if (!write_plane_used(d, g, pl) || gp[pl].band.rows < 1) continue;
+        base[pl] = static_cast<uint8_t*>(sl.d_out) + off[pl]; pit[pl] = (int64_t)pitch[pl];
+    }
+    hipError_t e = launch_grid_pad(gp, base, pit, st);
+    if (e != hipSuccess) return hip_fail(e, "grid_pad launch", AVIFGPU_writErr);
+    // every piece of every plane first: is its tile page-locked?  Asked once per tile plane and host call (c.pinned_tiles), over the whole
+    // tile plane -- a band meets a tile in one piece, and the bands of a save meet it again and again
+    struct Down { int pl; GridPiece k; uint8_t* dst; int64_t stride; bool pinned; };
+    std::vector<Down> downs;
+    bool pageable[4] = {}, any_pageable = false;
+    for (int pl = 0; pl < 4; ++pl) {
+        if (!base[pl]) continue;
+        const GridSavePlane& s = gp[pl];
+        grid_save_pieces(j.grid.grid, s.band, s.tw, s.th, s.b, [&](const GridPiece& k) {
+            const avifgpu_grid_tile& t = j.grid.tiles[k.tile];
+            auto seen = c.pinned_tiles.find(t.plane[pl]);
+            if (seen == c.pinned_tiles.end())
+                seen = c.pinned_tiles.emplace(t.plane[pl], is_pinned(t.plane[pl], (size_t)t.stride[pl] * (size_t)(s.th - 1) + (size_t)s.tw * (size_t)s.b)).first;
+            uint8_t* const dst = static_cast<uint8_t*>(const_cast<void*>(t.plane[pl])) + (int64_t)k.src_y * t.stride[pl] + k.src_x;
+            pageable[pl] = pageable[pl] || !seen->second;
+            downs.push_back({ pl, k, dst, t.stride[pl], seen->second });
+        });
+        any_pageable = any_pageable || pageable[pl];
+    }
+    if (any_pageable) { if (const int err = grow_pinned(&sl.h_planes, &sl.h_planes_cap, out_total)) return err; }
+    for (int pl = 0; pl < 4; ++pl) {                         // a plane with a pageable piece: all of its band into the bounce buffer, once
+        if (!pageable[pl]) continue;
+        const size_t rows = (size_t)(gp[pl].band.rows + gp[pl].band.pad_rows);
+        e = hipMemcpyAsync(static_cast<uint8_t*>(sl.h_planes) + off[pl], base[pl], pitch[pl] * rows, hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) return hip_fail(e, "D2H copy", AVIFGPU_writErr);
+    }
+    for (const Down& w : downs) {
+        const size_t at = (size_t)w.k.dst_y * pitch[w.pl] + (size_t)w.k.dst_x;
+        if (w.pinned) {
+            e = hipMemcpy2DAsync(w.dst, (size_t)w.stride, base[w.pl] + at, pitch[w.pl], (size_t)w.k.bytes, (size_t)w.k.rows, hipMemcpyDeviceToHost, st);
+            if (e != hipSuccess) return hip_fail(e, "D2H copy (tile piece)", AVIFGPU_writErr);
+        } else {
+            j.bounce.push_back({ w.dst, w.stride, off[w.pl] + at, pitch[w.pl], (size_t)w.k.bytes, w.k.rows });
+            c.bytes_bounced.fetch_add((uint64_t)w.k.bytes * (uint64_t)w.k.rows, std::memory_order_relaxed);
+        }
+        c.bytes_d2h.fetch_add((uint64_t)w.k.bytes * (uint64_t)w.k.rows, std::memory_order_relaxed);
+    }
+    return 0;
+}
+
 // Issue the copies and the launch of one tile on its slot's stream.  Returns an OSErr; the message is in this thread's
 // last_error().  After the first asynchronous operation any failure drains the stream before returning, so no DMA is left
 // running into (or out of) caller memory behind an error return.
@@ -491,12 +552,19 @@ int start_write(Ctx& c, Job& j)
     if ((err = grow_device(&sl.d_in, &sl.d_in_cap, in_pitch * (size_t)j.nrows))) return err;
     size_t off[4] = {}, pitch[4] = {}, out_total = 0;
     int prow[4] = {}; int64_t pbytes[4] = {};
+    GridSavePlane gp[4] = {};                                // a grid save: the band of every used plane
     for (int pl = 0; pl < 4; ++pl) {
         if (!write_plane_used(d, g, pl)) continue;
         write_plane_extent(d, g, pl, j.nrows, prow[pl], pbytes[pl]);
         pitch[pl] = staging_pitch((size_t)pbytes[pl]);
+        size_t rows = (size_t)prow[pl];
+        if (j.to_grid) {                                     // the padded pitch, and the pad rows below the last band
+            grid_save_plane(d, g, j.grid.grid, pl, j.row0, j.nrows, gp[pl]);
+            pitch[pl] = align256((size_t)gp[pl].full_bytes);
+            rows += (size_t)gp[pl].band.pad_rows;
+        }
         off[pl] = out_total;
-        out_total += align256(pitch[pl] * (size_t)prow[pl]);
+        out_total += align256(pitch[pl] * rows);
     }
     if ((err = grow_device(&sl.d_out, &sl.d_out_cap, out_total))) return err;
 
@@ -525,29 +593,33 @@ int start_write(Ctx& c, Job& j)
     }
     e = launch_write(p, d->depth, d->planes, g.dst16, d->output, g.xs, g.ys, hot_variant(), st, j.label);
     if (e != hipSuccess) { (void)hipStreamSynchronize(st); return hip_fail(e, "kernel launch", AVIFGPU_writErr); }
-    // planes back: straight into page-locked destinations, through the pinned bounce buffer otherwise
-    j.nbounce = 0;
-    bool any_pageable = false;
-    bool pinned_dst[4] = {};
-    for (int pl = 0; pl < 4; ++pl) {
-        if (!write_plane_used(d, g, pl) || prow[pl] == 0) continue;
-        const size_t span = (size_t)j.planes_out_stride[pl] * (size_t)(prow[pl] - 1) + (size_t)pbytes[pl];
-        pinned_dst[pl] = is_pinned(j.planes_out[pl], span);
-        any_pageable = any_pageable || !pinned_dst[pl];
-    }
-    if (any_pageable && (err = grow_pinned(&sl.h_planes, &sl.h_planes_cap, out_total))) { (void)hipStreamSynchronize(st); return err; }
-    for (int pl = 0; pl < 4; ++pl) {
-        if (!write_plane_used(d, g, pl) || prow[pl] == 0) continue;
-        const uint8_t* dev = static_cast<const uint8_t*>(sl.d_out) + off[pl];
-        if (pinned_dst[pl]) {
-            e = copy_rows(j.planes_out[pl], (size_t)j.planes_out_stride[pl], dev, pitch[pl], (size_t)pbytes[pl], (size_t)prow[pl], hipMemcpyDeviceToHost, st);
-        } else {
-            e = hipMemcpyAsync(static_cast<uint8_t*>(sl.h_planes) + off[pl], dev, pitch[pl] * (size_t)prow[pl], hipMemcpyDeviceToHost, st);
-            j.bounce[j.nbounce++] = { static_cast<uint8_t*>(j.planes_out[pl]), j.planes_out_stride[pl], off[pl], pitch[pl], (size_t)pbytes[pl], prow[pl] };
+    j.bounce.clear();
+    if (j.to_grid) {
+        if ((err = grid_planes_down(c, j, sl, g, gp, off, pitch, out_total))) { (void)hipStreamSynchronize(st); return err; }
+    } else {
+        // planes back: straight into page-locked destinations, through the pinned bounce buffer otherwise
+        bool any_pageable = false;
+        bool pinned_dst[4] = {};
+        for (int pl = 0; pl < 4; ++pl) {
+            if (!write_plane_used(d, g, pl) || prow[pl] == 0) continue;
+            const size_t span = (size_t)j.planes_out_stride[pl] * (size_t)(prow[pl] - 1) + (size_t)pbytes[pl];
+            pinned_dst[pl] = is_pinned(j.planes_out[pl], span);
+            any_pageable = any_pageable || !pinned_dst[pl];
         }
-        if (e != hipSuccess) { (void)hipStreamSynchronize(st); return hip_fail(e, "D2H copy", AVIFGPU_writErr); }
-        c.bytes_d2h.fetch_add((uint64_t)pbytes[pl] * (uint64_t)prow[pl], std::memory_order_relaxed);
-        if (!pinned_dst[pl]) c.bytes_bounced.fetch_add((uint64_t)pbytes[pl] * (uint64_t)prow[pl], std::memory_order_relaxed);
+        if (any_pageable && (err = grow_pinned(&sl.h_planes, &sl.h_planes_cap, out_total))) { (void)hipStreamSynchronize(st); return err; }
+        for (int pl = 0; pl < 4; ++pl) {
+            if (!write_plane_used(d, g, pl) || prow[pl] == 0) continue;
+            const uint8_t* dev = static_cast<const uint8_t*>(sl.d_out) + off[pl];
+            if (pinned_dst[pl]) {
+                e = copy_rows(j.planes_out[pl], (size_t)j.planes_out_stride[pl], dev, pitch[pl], (size_t)pbytes[pl], (size_t)prow[pl], hipMemcpyDeviceToHost, st);
+            } else {
+                e = hipMemcpyAsync(static_cast<uint8_t*>(sl.h_planes) + off[pl], dev, pitch[pl] * (size_t)prow[pl], hipMemcpyDeviceToHost, st);
+                j.bounce.push_back({ static_cast<uint8_t*>(j.planes_out[pl]), j.planes_out_stride[pl], off[pl], pitch[pl], (size_t)pbytes[pl], prow[pl] });
+            }
+            if (e != hipSuccess) { (void)hipStreamSynchronize(st); return hip_fail(e, "D2H copy", AVIFGPU_writErr); }
+            c.bytes_d2h.fetch_add((uint64_t)pbytes[pl] * (uint64_t)prow[pl], std::memory_order_relaxed);
+            if (!pinned_dst[pl]) c.bytes_bounced.fetch_add((uint64_t)pbytes[pl] * (uint64_t)prow[pl], std::memory_order_relaxed);
+        }
     }
     if (j.stats.any()) {
         // the statistics kernels on the tile that is already resident (no second upload), on the slot's stream BEHIND the planes' copies back:
@@ -642,18 +714,18 @@ int start_read(Ctx& c, Job& j)
     e = launch_read(p, d->colorspace, d->depth, g.alpha, g.xs, g.ys, st, j.label);
     if (e != hipSuccess) { (void)hipStreamSynchronize(st); return hip_fail(e, "kernel launch", AVIFGPU_readErr); }
 
-    j.nbounce = 0;
+    j.bounce.clear();
     const size_t dst_span = (size_t)j.rows_out_stride * (size_t)(j.nrows - 1) + row_bytes;
     if (j.rows_out == sl.h_rows || is_pinned(j.rows_out, dst_span)) {
         e = copy_rows(j.rows_out, (size_t)j.rows_out_stride, sl.d_out, out_pitch, row_bytes, (size_t)j.nrows, hipMemcpyDeviceToHost, st);
     } else {
         if ((err = grow_pinned(&sl.h_rows, &sl.h_rows_cap, out_pitch * (size_t)j.nrows))) { (void)hipStreamSynchronize(st); return err; }
         e = hipMemcpyAsync(sl.h_rows, sl.d_out, out_pitch * (size_t)j.nrows, hipMemcpyDeviceToHost, st);
-        j.bounce[j.nbounce++] = { static_cast<uint8_t*>(j.rows_out), j.rows_out_stride, 0, out_pitch, row_bytes, j.nrows };
+        j.bounce.push_back({ static_cast<uint8_t*>(j.rows_out), j.rows_out_stride, 0, out_pitch, row_bytes, j.nrows });
     }
     if (e != hipSuccess) { (void)hipStreamSynchronize(st); return hip_fail(e, "D2H copy", AVIFGPU_readErr); }
     c.bytes_d2h.fetch_add((uint64_t)row_bytes * (uint64_t)j.nrows, std::memory_order_relaxed);
-    if (j.nbounce) c.bytes_bounced.fetch_add((uint64_t)row_bytes * (uint64_t)j.nrows, std::memory_order_relaxed);
+    if (!j.bounce.empty()) c.bytes_bounced.fetch_add((uint64_t)row_bytes * (uint64_t)j.nrows, std::memory_order_relaxed);
     if ((e = hipEventRecord(sl.done, st)) != hipSuccess) { (void)hipStreamSynchronize(st); return hip_fail(e, "event record", AVIFGPU_readErr); }
     return 0;
 }
@@ -665,10 +737,7 @@ int finish(Ctx& c, Job& j)
     const hipError_t e = hipEventSynchronize(sl.done);
     if (e != hipSuccess) return hip_fail(e, "event synchronize", j.is_write ? AVIFGPU_writErr : AVIFGPU_readErr);
     const uint8_t* hb = static_cast<const uint8_t*>(j.is_write ? sl.h_planes : sl.h_rows);
-    for (int i = 0; i < j.nbounce; ++i) {
-        const Job::Bounce& b = j.bounce[i];
-        host_copy_rows(b.dst, (size_t)b.dst_stride, hb + b.off, b.pitch, b.bytes, (size_t)b.rows);
-    }
+    for (const Job::Bounce& b : j.bounce) host_copy_rows(b.dst, (size_t)b.dst_stride, hb + b.off, b.pitch, b.bytes, (size_t)b.rows);
     return 0;
 }
 
@@ -1010,17 +1079,22 @@ void* tile_buffer(int ctx, int slot, size_t bytes)
 }
 
 int write_tile_enqueue(int ctx, int slot, const avifgpu_write_desc* d, int row0, int nrows, const void* src, int64_t src_row_bytes,
-                       void* const dst[4], const int64_t dst_stride[4], const IccArgs& icc)
+                       void* const dst[4], const int64_t dst_stride[4], const IccArgs& icc, const GridDest* grid)
 {
     WriteGeom g;
     int err = check_write(d, row0, nrows, g);              // early, on the calling thread: parameter errors come back synchronously
     if (err) return err;
-    if ((err = check_write_buffers(d, g, nrows, src, src_row_bytes, dst, dst_stride))) return err;
+    if (grid) {                                            // the tiles are the destination, checked by whoever built the GridDest (check_grid_tiles): the rows only
+        if (!src || !grid->tiles) return fail(AVIFGPU_formatBadParameters, "null buffer");
+        const int64_t min_src_row = (int64_t)d->width * d->planes * (d->depth / 8);
+        if (src_row_bytes < min_src_row) return fail(AVIFGPU_formatBadParameters, "src_row_bytes %lld < %lld", (long long)src_row_bytes, (long long)min_src_row);
+    } else if ((err = check_write_buffers(d, g, nrows, src, src_row_bytes, dst, dst_stride))) return err;
     if (nrows == 0) return 0;
     Job j;
     j.is_write = true; j.slot = slot; j.wd = *d; j.row0 = row0; j.nrows = nrows;
     j.rows_in = src; j.rows_in_stride = src_row_bytes;
-    for (int pl = 0; pl < 4; ++pl) { j.planes_out[pl] = dst[pl]; j.planes_out_stride[pl] = dst_stride[pl]; }
+    if (grid) { j.to_grid = true; j.grid = *grid; }
+    else for (int pl = 0; pl < 4; ++pl) { j.planes_out[pl] = dst[pl]; j.planes_out_stride[pl] = dst_stride[pl]; }
     j.icc = icc;
     if ((err = save_stats_for_call(d, g, AVIFGPU_MEM_HOST, &j.stats))) return err;   // the arming is the calling thread's; a mismatch fails here, before anything is queued
     return enqueue(ctx, j);
@@ -1106,6 +1180,7 @@ int wait_all_impl(bool discard_hist)
         if (c->last_label[0]) set_last_kernel(c->last_label);
         if (c->err && !first) { first = c->err; snprintf(msg, sizeof(msg), "%s", c->err_msg); }
         c->err = 0; c->err_msg[0] = 0;
+        c->pinned_tiles.clear();
     }
     const int hrc = collect(discard_hist || first != 0);
     if (first) set_error(msg);
@@ -1139,7 +1214,7 @@ void host_call_lock() { g_host_call_mu.lock(); }
 void host_call_unlock() { g_host_call_mu.unlock(); }
 
 int write_rows_host(const avifgpu_write_desc* d, int row0, int nrows, const void* src, int64_t src_row_bytes,
-                    void* const dst[4], const int64_t dst_stride[4], const IccArgs& icc)
+                    void* const dst[4], const int64_t dst_stride[4], const IccArgs& icc, const GridDest* grid)
 {
     std::lock_guard<std::recursive_mutex> serial(g_host_call_mu);
     const int n = context_count();
@@ -1170,7 +1245,7 @@ int write_rows_host(const avifgpu_write_desc* d, int row0, int nrows, const void
                 tdst[pl] = dst[pl] ? static_cast<uint8_t*>(dst[pl]) + r * dst_stride[pl] : nullptr;
             }
             const uint8_t* tsrc = static_cast<const uint8_t*>(src) + (int64_t)(r0 - row0) * src_row_bytes;
-            if ((err = write_tile_enqueue(c, slot, d, r0, nr, tsrc, src_row_bytes, tdst, dst_stride, icc))) failed = true;
+            if ((err = write_tile_enqueue(c, slot, d, r0, nr, tsrc, src_row_bytes, tdst, dst_stride, icc, grid))) failed = true;
         }
         if (!any) break;
     }

@@ -30,6 +30,10 @@ struct IccArgs {
     const avifgpu_icc_pipeline32* p32 = nullptr;    // 32-bit documents behind a LUT-based profile: lcms2's stage program (avifgpu_write_rows_icc_pipeline32)
 };
 
+// The optional destination of a grid save (include/avifgpu.h "grid save"): the planes go to the padded tiles of `tiles` (host records of
+// host pointers, checked with check_grid_tiles of grid_save.h by whoever builds it: avifgpu_write_rows_grid, the shim) instead of dst[] / dst_stride[], which are then ignored.
+struct GridDest { avifgpu_grid grid; const avifgpu_grid_tile* tiles; };
+
 constexpr int kLabelBytes = 192;                    // kernel label buffers handed to launch_*()
 
 struct WriteGeom { bool color, alpha, dst16; int xs, ys, nplanes; };
@@ -45,6 +49,9 @@ void set_last_kernel(const char* label);
 bool icc_pipeline32_stamped(const avifgpu_icc_pipeline32* p);      // proven, and unchanged since
 
 int  check_write(const avifgpu_write_desc* d, int row0, int nrows, WriteGeom& g);
+// what every avifgpu_write_rows* entry is behind its own checks: validation, the armed statistics, the launch or the host scheduler
+int  write_rows_with_icc(const avifgpu_write_desc* d, const IccArgs& icc, int32_t row0, int32_t nrows, const void* src, int64_t src_row_bytes,
+                         void* const dst[4], const int64_t dst_stride[4], int32_t mem_kind, void* stream);
 int  check_write_buffers(const avifgpu_write_desc* d, const WriteGeom& g, int nrows, const void* src, int64_t src_row_bytes,
                          void* const dst[4], const int64_t dst_stride[4]);
 // Kernel parameters of one tile.  Uploads ICC tables to the CURRENT device's cache when they changed.
@@ -180,7 +187,7 @@ void* tile_buffer(int ctx, int slot, size_t bytes);
 // Host pointers only.  `src` / `dst` may be pinned (DMA goes straight to them) or pageable (the worker bounces them through
 // the slot's pinned buffers with its own memcpy, off the calling thread).
 int  write_tile_enqueue(int ctx, int slot, const avifgpu_write_desc* d, int row0, int nrows, const void* src, int64_t src_row_bytes,
-                        void* const dst[4], const int64_t dst_stride[4], const IccArgs& icc);
+                        void* const dst[4], const int64_t dst_stride[4], const IccArgs& icc, const GridDest* grid = nullptr);
 int  read_tile_enqueue(int ctx, int slot, const avifgpu_read_desc* d, int row0, int nrows, const void* const src[4],
                        const int64_t src_stride[4], void* dst, int64_t dst_row_bytes);
 int  wait_slot(int ctx, int slot);                   // the tile last queued on (ctx, slot) has fully landed in host memory
@@ -199,7 +206,7 @@ int  topology_probe_c(const char* sysfs_root, const char* bdf, int32_t* numa_nod
 // Whole-range host conversions: rows [row0, row0 + nrows) are cut into one contiguous row tile per context (even cuts) and
 // each tile is pipelined through that context's slots in sub-tiles.  Output bytes do not depend on the number of contexts.
 int  write_rows_host(const avifgpu_write_desc* d, int row0, int nrows, const void* src, int64_t src_row_bytes,
-                     void* const dst[4], const int64_t dst_stride[4], const IccArgs& icc);
+                     void* const dst[4], const int64_t dst_stride[4], const IccArgs& icc, const GridDest* grid = nullptr);
 int  read_rows_host(const avifgpu_read_desc* d, int row0, int nrows, const void* const src[4], const int64_t src_stride[4],
                     void* dst, int64_t dst_row_bytes);
 

@@ -87,6 +87,8 @@ HOST_ABI = [
                                                             c_int32, c_void_p, POINTER(Image)]),
     ("avifgpu_host_create_heif_image_with_pipeline", c_int16, [POINTER(FormatRecord), c_int32, POINTER(SaveUIOptions), c_int32, c_int32,
                                                                c_int32, c_void_p, POINTER(Image)]),
+    ("avifgpu_host_create_heif_image_grid", c_int16, [POINTER(FormatRecord), c_int32, POINTER(SaveUIOptions), c_int32, c_int32,
+                                                      c_int32, c_void_p, POINTER(Image)]),   # c_void_p: const avifgpu_grid* (Grid of the package); columns * rows Images
     ("avifgpu_host_read_heif_image", c_int16, [POINTER(Image), c_int32, POINTER(Nclx), POINTER(LoadUIOptions),
                                                POINTER(FormatRecord)]),
     ("avifgpu_host_read_heif_image_oriented", c_int16, [POINTER(Image), c_int32, c_int32, POINTER(Nclx), POINTER(LoadUIOptions),

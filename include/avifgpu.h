@@ -1014,6 +1014,87 @@ int32_t avifgpu_probe_grid_gather(const avifgpu_grid_tile* tiles_dev, int32_t co
                                   int32_t tile_h_samples, int32_t bytes_per_sample, int32_t x0, int32_t y0, int32_t w, int32_t h,
                                   void* dst, int64_t dst_row_bytes, void* stream);
 
+/* ---- grid save: a save written straight into the padded tiles of a grid -------------------------------------------------------------------
+ * The cap on a coded frame that makes large pictures grids on the way in holds on the way out: a document larger than one coded frame
+ * reaches the encoder as columns x rows tile images of one size.  The grid save is the exact mirror of avifgpu_read_rows_grid.
+ * With desc an avifgpu_write_desc (its width x height is the canvas), P_pl the plane pl the corresponding avifgpu_write_rows* call writes
+ * for it -- pw x ph "pixels" of b = bytes_per_sample * samples_per_pixel bytes (avifgpu_write_plane_geometry; b is 1, 2, 3, 4, 6 or 8: the
+ * interleaved AVIFGPU_OUT_REFERENCE colour plane moves whole pixels) -- xs, ys the chroma shifts of AVIFGPU_OUT_YCBCR output (0 otherwise)
+ * and a tile's plane pl holding tw_p x th_p pixels ((tile_width, tile_height) for luma, alpha and interleaved planes,
+ * ((tile_width + xs) >> xs, (tile_height + ys) >> ys) for chroma), the PADDED plane is the canvas plane replicated at its right and
+ * bottom edge,
+ *     Q_pl[y, x] = P_pl[min(y, ph - 1), min(x, pw - 1)]      over (rows * th_p) x (columns * tw_p),
+ * and the tiles are
+ *     tile[r * columns + c].plane[pl][y, x] = Q_pl[r * th_p + y, c * tw_p + x].
+ * Edge replication is an EXTENSION of this library, like AVIFGPU_DOWNSAMPLE_AVERAGE: the reference writes no grids, and no encoder's own
+ * padding rule was verified against it.
+ * Legal grids for a save: those of the grid open (above), applied to the write descriptor's shifts, in which every tile also has a visible
+ * sample: (columns - 1) * tile_width < width and (rows - 1) * tile_height < height.  Then every sample of every tile is written exactly
+ * once per save -- an encoder is never handed a tile nobody wrote.
+ * A call converts rows [row0, row0 + nrows) under avifgpu_write_rows' own rule for row0 and nrows and writes, in every used plane, the
+ * plane rows of that range over all columns * tw_p pixels; the call whose range ends at `height` also writes the rows below ph.  So the
+ * bytes of a tile do not depend on how the rows were cut into calls.  Bytes of a tile row beyond tw_p * b are never touched.
+ * Byte equality: the tiles equal, byte for byte, the split of Q built from the plain save of the same descriptor, ICC stage and source into
+ * planes whose base and stride are multiples of 256.  (The multiples of 256 matter for one case only: a 32-bit document behind an ICC
+ * transform may take the streaming or the generic kernel depending on alignment, which agree within tier 2 -- see avifgpu_set_hot_variant.)
+ * An armed code histogram, thumbnail and summary see the canvas, never the padding: what the same arms receive from the plain save. */
+enum { AVIFGPU_ICC_KIND_NONE = 0,          /* icc must be NULL */
+       AVIFGPU_ICC_KIND_TRANSFORM = 1,     /* const avifgpu_icc_transform*   (avifgpu_write_rows_icc) */
+       AVIFGPU_ICC_KIND_SAMPLED = 2,       /* const avifgpu_icc_sampled32*   (avifgpu_write_rows_icc_sampled) */
+       AVIFGPU_ICC_KIND_SHAPER8 = 3,       /* const avifgpu_icc_shaper8*     (avifgpu_write_rows_icc8) */
+       AVIFGPU_ICC_KIND_CLUT16 = 4,        /* const avifgpu_icc_clut16*      (avifgpu_write_rows_icc16) */
+       AVIFGPU_ICC_KIND_CLUT8_TABLE = 5,   /* const avifgpu_icc_clut16*      (avifgpu_write_rows_icc8_table) */
+       AVIFGPU_ICC_KIND_PIPELINE32 = 6 };  /* const avifgpu_icc_pipeline32*  (avifgpu_write_rows_icc_pipeline32; must be stamped) */
+
+/* 0 where desc and grid are what avifgpu_write_rows_grid takes; formatBadParameters (or what the descriptor's own check returns) with a
+ * message otherwise.  Host only. */
+int32_t avifgpu_write_grid_check(const avifgpu_write_desc* desc, const avifgpu_grid* grid);
+
+/* Device scratch that a MEM_DEVICE call of `nrows` rows needs -- the entry asks for exactly this value:
+ *     256  +  sum over the used planes of  align256(row bytes of the canvas plane) * plane rows of nrows
+ * (plane rows: (nrows + ys) >> ys for chroma).  0 for nrows == 0; a negative OSErr for a bad descriptor or row count.  Host only. */
+int64_t avifgpu_write_grid_scratch_bytes(const avifgpu_write_desc* desc, int32_t nrows);
+
+/* The grid with the fewest tiles whose tiles are multiples of `align` and at most max_tile_width x max_tile_height: `columns` is the
+ * smallest value for which some multiple of align is at most max_tile_width and at least ceil(width / columns), tile_width the smallest
+ * such multiple; align is raised to even where that direction is subsampled and columns > 1; rows alike.  formatBadParameters where none
+ * exists or a side would exceed 256.  The result is always legal and minimal: were (columns - 1) * tile_width >= width, tile_width would
+ * have qualified columns - 1, which was tried first.  Host only. */
+int32_t avifgpu_grid_fit(const avifgpu_write_desc* desc, int32_t max_tile_width, int32_t max_tile_height, int32_t align, avifgpu_grid* grid);
+
+/* The ImageGrid item payload of (grid, width x height), the inverse of avifgpu_grid_parse: 8 bytes, or 12 with flags bit 0 where a size
+ * exceeds 65 535.  Returns the byte count; formatBadParameters for a null argument, a side outside 1..256, a size below 1, too little
+ * capacity.  Host only. */
+int32_t avifgpu_grid_payload(const avifgpu_grid* grid, int32_t width, int32_t height, uint8_t* out, int64_t capacity);
+
+/* Save rows [row0, row0 + nrows) into the tiles.  icc_kind says which prepared structure `icc` points to (NONE: NULL); the checks of the
+ * corresponding avifgpu_write_rows* entry apply.  `tiles` holds columns * rows records and lives where mem_kind says:
+ *   AVIFGPU_MEM_DEVICE  a device pointer to records of device pointers; the library never reads it on the host.  The unchanged save runs on
+ *     `stream` into the head of scratch (planes at 256-byte-aligned bases, pitch align256(row bytes)), any armed statistics behind it on
+ *     the caller's device arms, then grid_scatter -- a byte mover, a code object of its own; one launch, two for subsampled chroma --
+ *     puts the band of every used plane into the tiles, padding included.  Nothing synchronises.
+ *   AVIFGPU_MEM_HOST    a host array of host pointers; scratch is ignored.  The bound contexts' row-tile scheduler converts as for
+ *     avifgpu_write_rows, pads in place on the device and sends every band down as one strided copy per tile piece: straight into
+ *     page-locked tiles, through the pinned bounce buffer into pageable ones.  The bytes are the same for every number of bound contexts.
+ *     A NULL pointer or a stride below the row for a used plane of any tile is refused before anything is queued.
+ * Where samples are 16 bits (bit depth above 8) every tile plane and stride is a multiple of 2, as every plane of 16-bit samples in this
+ * interface is; MEM_HOST refuses an odd one, a device table is the caller's to keep so.
+ * formatBadParameters before anything is launched for an illegal or non-minimal grid, NULL tiles, an unknown kind, a bad row range, less
+ * scratch than the helper's value (DEVICE), a bad mem_kind. */
+int32_t avifgpu_write_rows_grid(const avifgpu_write_desc* desc, int32_t icc_kind, const void* icc, const avifgpu_grid* grid,
+                                const avifgpu_grid_tile* tiles, int32_t row0, int32_t nrows, const void* src, int64_t src_row_bytes,
+                                void* scratch, int64_t scratch_bytes, int32_t mem_kind, void* stream);
+
+/* Measuring and testing aid (tools/bench_grid_save.py): the scatter kernel ALONE on one plane.  The plane holds plane_w x plane_h pixels of
+ * bytes_per_pixel (1, 2, 3, 4, 6 or 8) bytes; rows [y0, y0 + h) of its PADDED plane (y0 < plane_h; the rows at and below plane_h are row
+ * plane_h - 1 again) go to tiles_dev[...].plane[plane] (tile_w_pixels x tile_h_pixels each, `columns` to a row; the table must hold the
+ * tile rows those rows touch).  `src` is plane row y0, rows src_row_bytes apart, at any address -- at any EVEN address and
+ * row distance, like the tile planes, for the pixel sizes 2, 6 and 8, which are 16-bit samples and are moved as such at seams and in the
+ * padding; on `stream`. */
+int32_t avifgpu_probe_grid_scatter(const avifgpu_grid_tile* tiles_dev, int32_t columns, int32_t plane, int32_t tile_w_pixels,
+                                   int32_t tile_h_pixels, int32_t bytes_per_pixel, int32_t plane_w, int32_t plane_h, int32_t y0, int32_t h,
+                                   const void* src, int64_t src_row_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

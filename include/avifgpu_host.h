@@ -176,6 +176,16 @@ avifgpu_OSErr avifgpu_host_create_heif_image_with_pipeline(avifgpu_FormatRecord*
                                                            int32_t matrix_coefficients, int32_t color_primaries,
                                                            const avifgpu_icc_pipeline32* documentPipeline, avifgpu_image* img);
 
+/* The grid save (include/avifgpu.h "grid save") behind the same tile protocol: the planes go to `tiles`, columns * rows images of
+ * tile_width x tile_height in row-major order, each described and (where its plane[0] is NULL) allocated like img of the plain entry and
+ * freed with avifgpu_image_free; the samples beyond the canvas replicate its right and bottom edge.  Everything else is as for
+ * avifgpu_host_create_heif_image: the tile requests, abortProc, the ICC decision from the record's profile, the armed statistics (which
+ * see the canvas only).  AVIFGPU_formatBadParameters for a NULL grid or tiles and for a grid avifgpu_write_grid_check refuses. */
+avifgpu_OSErr avifgpu_host_create_heif_image_grid(avifgpu_FormatRecord* formatRecord, int32_t alphaState,
+                                                  const avifgpu_SaveUIOptions* saveOptions, int32_t output,
+                                                  int32_t matrix_coefficients, int32_t color_primaries,
+                                                  const avifgpu_grid* grid, avifgpu_image* tiles);
+
 /*
  * Read direction: one entry for the six ReadHeifImage{Gray,RGB}{Eight,Sixteen,ThirtyTwo}Bit functions
  * (dispatch as DoReadContinue, Read.cpp:587-630; host depth from formatRecord->depth).  Sets loPlane/hiPlane/
