@@ -127,24 +127,30 @@ AG_DEV float fast_linear_to_pq(float value, float mult)
 // m1 E is EXACT in float (m1 = 2610 / 2^14 has 12 significant bits, |E| < 2^8), so are N and F; the one rounded number the exponent
 // sees is below 0.66 in magnitude and v_log_f32 gets an argument in [0.5, 1).  Round 3 formed E, m, N and F with v_frexp_*, v_floor,
 // v_cvt and v_ldexp: +8 issue slots per sample, which the 10-bit RGB kernels could not pay (0.777 -> 0.70 of 8 TB/s).  Round 4:
-//   * F and 2^N come from two 512-entry float tables in LDS indexed by the SIGN + EXPONENT FIELD of t (v_lshrrev + v_and + two
+//   * F and 2^N come from two 256-entry float tables in LDS indexed by the EXPONENT FIELD of t alone (v_lshrrev + v_and + two
 //     ds_read_b32; two tables rather than one of records so that the values of two samples can sit in adjacent registers, the
-//     operand form of the packed instructions); the entries of zero / denormal t, of negative t (sign bit set) and of inf / NaN
-//     have N = -100 -- q = c1, code 0, what the reference stores for a negative sample and what this library stores for NaN
-//      -- so no clamp, no special case and no NaN ever reaches the quotient;
-//   * m is the mantissa field under the exponent of 0.5 (one v_and_or_b32);
+//     operand form of the packed instructions); the entries of zero / denormal t and of inf / NaN (fields 0 and 255) have
+//     N = -100 -- q = c1, code 0, what this library stores for NaN -- so no clamp and no special case;
+//   * m is the mantissa field under the exponent of 0.5 WITH t's SIGN (one v_and_or_b32, mask 0x807fffff).  The sign rule: a
+//     sample with the sign bit set -- negative, -0, -inf, a sign-set NaN -- hands v_log_f32 a negative argument, the result is
+//     NaN, NaN flows through every later operation, and the clamp of the last v_exp_f32 returns 0 under DX10_CLAMP: code 0, what
+//     the reference stores for a negative sample, by the mechanism the compact form relies on (AG_PQ_MAX0 above).  So the tables
+//     need no entry for a set sign bit (the 512-entry tables of rounds 4-6 held 256 more, all F = 0, N = -100, for nothing but this code 0);
+//     a positive sample reads the entries and runs the instructions it always did;
 //   * x = 2^(m1 log2 m + F) * 2^N is an exact scaling (a power of two moves no mantissa bit; nothing is near the ends of the
 //     exponent range), one packed multiply for two samples;
 //   * N = rint(m1 E) instead of floor: the exponent that the FMA rounds is half as large.
 // +3 plain and +1 packed issue slots per sample over the compact form, and CLOSER: codes that differ from the reference's on the
 // 900 k-sample sweep, 12 bit / 80 nits: 0.234 % (compact) -> 0.068 % (round 3) -> 0.041 %; at 10 bit 0.063 % -> 0.016 % -> 0.012 %.
 // The tables' contents are exact integer arithmetic on the exponent field (m1 E = 2610 E / 2^14), evaluated at COMPILE time into a
-// 4 KiB constant of the code object; a workgroup copies it into its LDS with 16-byte loads and stores (computing it in the prologue
-// cost ~80 VALU instructions per workgroup -- 13 % of the RGB f32 kernel, whose waves convert one span each).
-// (the pads keep the tables at offsets that ds_read2st64_b32 cannot express: merged into one two-dword read, F and the multiplier
-// of one sample land in adjacent registers and the packed instructions need moves)
+// 2 KiB constant of the code object (2 x 256 floats back to back = 128 float4); a workgroup copies it into its LDS with 16-byte
+// loads and stores, ONE per thread at 128 threads, half the threads at 256, two per thread for a single wave (computing it in the
+// prologue cost ~80 VALU instructions per workgroup -- 13 % of the RGB f32 kernel, whose waves convert one span each).
+// (in LDS a 16-byte gap keeps the tables at offsets that ds_read2st64_b32 cannot express: merged into one two-dword read, F and the
+// multiplier of one sample land in adjacent registers and the packed instructions need moves.  The gap is never copied:
+// pq_tab_lds_vec() maps float4 i of the constant to its place.)
 // AG_PQ_TAB_FORM (profiles/r04/pq_table_forms_ab.txt: the three are within a percent of each other on every row; 2 is the default --
-// fewest LDS instructions among the packed ones, 4 KiB): 3 = tables F, c2 2^N, c3 2^N (three ds_read_b32 per sample, N(x) and D(x)
+// fewest LDS instructions among the packed ones, 2 KiB): 3 = tables F, c2 2^N, c3 2^N (three ds_read_b32 per sample, N(x) and D(x)
 // formed without x: c2 x == (c2 2^N) y bit for bit); 2 = tables F, 2^N (two reads, x = y 2^N as a packed multiply); 1 = one table
 // of {F, 2^N} records (one ds_read_b64, but the values of two samples are not adjacent: the exponent FMA and the multiply are not packed).
 // (A form WITHOUT the first two transcendentals -- x from a 1024-entry table of 2^(m1 E) c_j^m1 and a cubic in the mantissa's offset
@@ -158,20 +164,22 @@ AG_DEV float fast_linear_to_pq(float value, float mult)
 #ifndef AG_PQ_ND_FMA
 #define AG_PQ_ND_FMA 0
 #endif
-constexpr int kPqTabEntries = 512;
-constexpr int kPqTabPad = 4;
+constexpr int kPqTabEntries = 256;                                       // one entry per exponent field; the sign never reaches the index
+constexpr int kPqTabPad = 4;                                             // in LDS only: the constant of the code object carries no pad
 constexpr int kPqTabCount = AG_PQ_TAB_FORM == 3 ? 3 : 2;
-struct PqExpTable { float t[kPqTabCount][kPqTabEntries + kPqTabPad]; };
-constexpr int kPqTabFloats = kPqTabCount * (kPqTabEntries + kPqTabPad);
+constexpr int kPqTabGap = AG_PQ_TAB_FORM == 1 ? 0 : kPqTabPad;           // (records are one table of 512 floats: nothing to keep apart)
+struct PqExpTable { float t[kPqTabCount][kPqTabEntries]; };
+constexpr int kPqTabConstFloats = kPqTabCount * kPqTabEntries;           // the constant: 2 x 256 floats back to back = 128 float4
+constexpr int kPqTabFloats = kPqTabCount * kPqTabEntries + (kPqTabCount - 1) * kPqTabGap;   // the LDS array: a gap between two tables
 constexpr float pq_pow2(int n) { float v = 1.0f; for (int i = 0; i < (n < 0 ? -n : n); ++i) v = n < 0 ? v * 0.5f : v * 2.0f; return v; }
 constexpr PqExpTable make_pq_exp_table()
 {
     PqExpTable t{};
     for (int i = 0; i < kPqTabEntries; ++i) {
-        const int eb = i & 255;
+        const int eb = i;
         float F = 0.0f;
-        int N = -100;                                                     // 0, denormal, negative, inf, NaN: x = 2^-100 * [0.63, 1.42)
-        if (i < 256 && eb != 0 && eb != 255) {
+        int N = -100;                                                     // 0, denormal, inf, NaN: x = 2^-100 * [0.63, 1.42)
+        if (eb != 0 && eb != 255) {
             const long long num = 2610LL * (eb - 126);                    // m1 E * 2^14; eb - 126 = the frexp exponent of a normal number
             long long n = (num + 8192) >> 14;                             // floor(m1 E + 1/2)
             if (((num + 8192) & 16383) == 0 && (n & 1)) n -= 1;           // ties to even, like rintf (never happens: 2610 E is not an odd multiple of 2^13)
@@ -180,12 +188,15 @@ constexpr PqExpTable make_pq_exp_table()
         }
         if (AG_PQ_TAB_FORM == 3) { t.t[0][i] = F; t.t[1][i] = kPqC2 * pq_pow2(N); t.t[kPqTabCount - 1][i] = kPqC3 * pq_pow2(N); }   // exact scalings
         else if (AG_PQ_TAB_FORM == 2) { t.t[0][i] = F; t.t[1][i] = pq_pow2(N); }
-        else { constexpr int W = kPqTabEntries + kPqTabPad; t.t[(2 * i) / W][(2 * i) % W] = F; t.t[(2 * i + 1) / W][(2 * i + 1) % W] = pq_pow2(N); }   // records
+        else { constexpr int W = kPqTabEntries; t.t[(2 * i) / W][(2 * i) % W] = F; t.t[(2 * i + 1) / W][(2 * i + 1) % W] = pq_pow2(N); }   // records
     }
     return t;
 }
 __device__ __attribute__((aligned(16))) const PqExpTable kPqExpTableConst = make_pq_exp_table();
-static_assert(sizeof(PqExpTable) == kPqTabFloats * sizeof(float) && kPqTabFloats % 4 == 0, "copied as float4");
+static_assert(sizeof(PqExpTable) == kPqTabConstFloats * sizeof(float) && kPqTabEntries % 4 == 0 && kPqTabGap % 4 == 0, "copied as float4");
+constexpr int kPqTabVec = kPqTabConstFloats / 4;                          // float4 to copy: 128 (three tables: 192)
+// float4 i of the constant -> its float4 place in LDS: table i / 64 starts kPqTabGap floats behind the end of the one before it
+AG_DEV int pq_tab_lds_vec(int i) { return i + (i / (kPqTabEntries / 4)) * (kPqTabGap / 4); }
 // The table of the calling kernel's workgroup (a function-local __shared__ array is one LDS allocation per kernel that reaches it).
 AG_DEV float* pq_exp_table()
 {
@@ -198,7 +209,7 @@ AG_DEV void pq_exp_table_fill(int tid, int nthreads)
     typedef float f4 __attribute__((ext_vector_type(4)));
     f4* dst = reinterpret_cast<f4*>(pq_exp_table());
     const f4* src = reinterpret_cast<const f4*>(&kPqExpTableConst);
-    for (int i = tid; i < kPqTabFloats / 4; i += nthreads) dst[i] = src[i];
+    for (int i = tid; i < kPqTabVec; i += nthreads) dst[pq_tab_lds_vec(i)] = src[i];
 }
 // The same fill in two steps, for the streaming kernels: a workgroup that copies its table BEFORE it asks for its pixels keeps every
 // wave's slot empty-handed for one L2 round trip + a barrier (about a microsecond of a wave's ~12).  load() issues the table's global
@@ -206,7 +217,7 @@ AG_DEV void pq_exp_table_fill(int tid, int nthreads)
 // first, the wait in front of the LDS writes is vmcnt(span loads), not vmcnt(0)); the caller synchronises with pq_table_barrier().
 template <int NTHREADS> struct PqTableFill {
     typedef float f4 __attribute__((ext_vector_type(4)));
-    static constexpr int kVec = kPqTabFloats / 4, N = (kVec + NTHREADS - 1) / NTHREADS;
+    static constexpr int kVec = kPqTabVec, N = (kVec + NTHREADS - 1) / NTHREADS;     // one round at 128 and 256 threads, two at 64
     f4 v[N];
     AG_DEV void load(int tid)
     {
@@ -221,24 +232,27 @@ template <int NTHREADS> struct PqTableFill {
 #pragma unroll
         // no test here either: the threads past the table's end hold its last entry (load()) and write it to its own place again -- a store
         // under a branch is where the optimiser sinks the table's LOAD to, behind the span loads, and the wait becomes vmcnt(0)
-        for (int i = 0; i < N; ++i) { const int idx = tid + i * NTHREADS; dst[idx < kVec ? idx : kVec - 1] = v[i]; }
+        for (int i = 0; i < N; ++i) { const int idx = tid + i * NTHREADS; dst[pq_tab_lds_vec(idx < kVec ? idx : kVec - 1)] = v[i]; }
     }
 };
 // LDS writes of this wave done, then the workgroup's barrier -- and NOT __syncthreads(): its fences cover global memory too and make the
 // compiler wait for every outstanding global load (s_waitcnt vmcnt(0)) in front of the barrier, which is the wait this split avoids.
+// A workgroup of ONE wave filled the table by itself: the fences alone (the wave's LDS writes done before its reads), no wait on other waves.
+template <int NTHREADS>
 AG_DEV void pq_table_barrier()
 {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
+    if constexpr (NTHREADS > 64) __builtin_amdgcn_s_barrier(); else __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
-AG_DEV uint32_t pq_tab_offset(float t) { return (__float_as_uint(t) >> (AG_PQ_TAB_FORM == 1 ? 20 : 21)) & (AG_PQ_TAB_FORM == 1 ? 0xff8u : 0x7fcu); }   // byte offset of t's entry
+AG_DEV uint32_t pq_tab_offset(float t) { return (__float_as_uint(t) >> (AG_PQ_TAB_FORM == 1 ? 20 : 21)) & (AG_PQ_TAB_FORM == 1 ? 0x7f8u : 0x3fcu); }   // byte offset of the entry of t's exponent field
+static_assert((0x3fcu >> 2) == kPqTabEntries - 1 && (0x7f8u >> 3) == kPqTabEntries - 1, "the index is the exponent field alone: no form reads past its table");
 AG_DEV float pq_tab_at(const float* tab, int which, uint32_t off)
 {
     if (AG_PQ_TAB_FORM == 1) return *reinterpret_cast<const float*>(reinterpret_cast<const uint8_t*>(tab + which) + off);
-    return *reinterpret_cast<const float*>(reinterpret_cast<const uint8_t*>(tab + which * (kPqTabEntries + kPqTabPad)) + off);
+    return *reinterpret_cast<const float*>(reinterpret_cast<const uint8_t*>(tab + which * (kPqTabEntries + kPqTabGap)) + off);
 }
-AG_DEV float pq_mantissa(float t) { return __uint_as_float((__float_as_uint(t) & 0x007fffffu) | 0x3f000000u); }
+AG_DEV float pq_mantissa(float t) { return __uint_as_float((__float_as_uint(t) & 0x807fffffu) | 0x3f000000u); }   // +-[0.5, 1): t's sign goes to v_log_f32
 // pq in [0, 1] for t = value * mult
 AG_DEV float fast_linear_to_pq01_hi(float value, float mult)
 {

@@ -1424,11 +1424,19 @@ __global__ __launch_bounds__(AG_WPX_BLOCK) void write_px(const WriteParams p)
 #define AG_STREAM_BLOCK 128
 #endif
 constexpr int kStreamWaves = AG_STREAM_BLOCK / 64;
-// ... and 256 for the interleaved f32 hand-off: on fresh data 0.782-0.789 -> 0.796-0.801 of 8 TB/s at 8192^2 with nothing else moved
-// (profiles/r05/workgroup_size_fresh_data_ab.txt; the 16-bit kernels and the integer hand-off are indifferent and stay at 128)
+// The interleaved f32 hand-off (write_f32_ref_stream) and gray + alpha (write_ga_stream) went to 256 in round 5: on fresh data 0.782-0.789 ->
+// 0.796-0.801 of 8 TB/s at 8192^2 with nothing else moved (profiles/r05/workgroup_size_fresh_data_ab.txt; the 16-bit kernels and the
+// integer hand-off are indifferent and stay at 128).  With the 2-KiB PQ exponent table (device_math.h) the hand-off runs from ONE wave:
+// it copies the table with two loads and two LDS writes and waits for nobody (pq_table_barrier<64> is a fence).  Measured on two boxes
+// (profiles/pq_half_table/): the four-wave workgroup LOST 1.5-3 % on the hand-off rows with the smaller table (128 threads the same),
+// the single wave is level with or ahead of the 4-KiB parent on every row (16384^2 hand-off +4 %).  write_ga_stream keeps its 256.
 #ifndef AG_F32_REF_BLOCK
-#define AG_F32_REF_BLOCK 256
+#define AG_F32_REF_BLOCK 64
 #endif
+#ifndef AG_GA_BLOCK
+#define AG_GA_BLOCK 256
+#endif
+constexpr int kGaWaves = AG_GA_BLOCK / 64;
 constexpr int kF32RefWaves = AG_F32_REF_BLOCK / 64;
 
 typedef float    f32x4 __attribute__((ext_vector_type(4)));
@@ -1660,11 +1668,21 @@ template <bool NT, typename V> AG_DEV void stream_store(V* p, V v)
 #ifndef AG_IREF_BUFFER
 #define AG_IREF_BUFFER 1      /* round 5: 0 = 64-bit lane pointers under a per-vector test, 1 = loads through a buffer resource of the row (RGBA: stores too), 2 = stores too everywhere */
 #endif
-// A/B switches of round 5's last experiment (profiles/r05/probe_shapes.txt: the bare pattern runs 4-8 % faster from 64- / 128-thread
-// workgroups and as global_load / global_store than from 256 threads through buffer resources): the workgroup of THIS kernel, and
-// whole spans addressed with 64-bit lane pointers (the ragged last span of a row keeps the buffer form).
+// The workgroup of THIS kernel (profiles/pq_half_table/; the question profiles/r05/probe_shapes.txt left open).  Two shapes, chosen per
+// launch by where the spans lie:
+//  * AG_HOT444_BLOCK_LINES (128 threads, two waves): every span starts and ends on a 128-byte line of the source and of the planes --
+//    a flat tile, or rows whose strides are multiples of 128 bytes, from bases that are.  The memory system serves this pattern 4-8 %
+//    faster from two-wave workgroups than from four-wave ones (the math-free twin, bench.py --full); with the PQ table copied in ONE
+//    load and one LDS write per thread the kernel follows: 8192^2 +1-3 %, 16384^2 +4-7 %.
+//  * AG_HOT444_BLOCK (256 threads, four waves): rows that start in the middle of a line (an odd width behind 16-byte aligned strides).
+//    Neighbouring spans then SHARE the line their border falls in, and the smaller the workgroup, the more of those borders lie between
+//    workgroups -- on other CUs, other XCDs, other L2s: 6001 x 4001 measured -5 % at 128 threads and -8 % at 64.
+// AG_HOT444_GLOBAL (A/B, off): whole spans addressed with 64-bit lane pointers (the ragged last span of a row keeps the buffer form).
 #ifndef AG_HOT444_BLOCK
 #define AG_HOT444_BLOCK AG_F32_STREAM_BLOCK
+#endif
+#ifndef AG_HOT444_BLOCK_LINES
+#define AG_HOT444_BLOCK_LINES 128
 #endif
 #ifndef AG_MEASURE
 #define AG_MEASURE 0          /* 1: measuring knobs that read the environment (AVIFGPU_DEBUG_LDS_PAD) are compiled in */
@@ -1672,11 +1690,13 @@ template <bool NT, typename V> AG_DEV void stream_store(V* p, V v)
 #ifndef AG_HOT444_GLOBAL
 #define AG_HOT444_GLOBAL 0
 #endif
-constexpr int kHot444Waves = AG_HOT444_BLOCK / 64;
-template <int TRANSFER, int PXL, bool NT>
-__global__ __launch_bounds__(AG_HOT444_BLOCK) AG_F32_SGPRS void write_rgb32_ycbcr444_hot(const WriteParams p)
+static_assert(AG_HOT444_BLOCK % 64 == 0 && AG_HOT444_BLOCK_LINES % 64 == 0, "whole waves");
+// launch_bounds = the workgroup the launcher picked; LDS: a strip per wave (3 KiB at 8 pixels a lane) + the 2-KiB PQ table, i.e. 14 KiB at
+// 256 threads, 8 KiB at 128
+template <int TRANSFER, int PXL, bool NT, int BLOCK>
+__global__ __launch_bounds__(BLOCK) AG_F32_SGPRS void write_rgb32_ycbcr444_hot(const WriteParams p)
 {
-    constexpr int WPB = kHot444Waves;
+    constexpr int WPB = BLOCK / 64;
     constexpr int K = 3 * PXL / 4;               // float4 per lane per span
     constexpr int SPAN_PX = 64 * PXL;
     constexpr int SPAN_DW = AG_HOT_F32_STRIP ? SpanStrip<K>::kDwords : SPAN_PX * 3 / 2;     // floats (half a span) | packed u16 codes
@@ -1688,7 +1708,7 @@ __global__ __launch_bounds__(AG_HOT444_BLOCK) AG_F32_SGPRS void write_rgb32_ycbc
     // AG_HOT_PRIO: a wave's instruction priority raised until its span loads have left (1); 2 = again for its last stage (measured: no gain)
     constexpr bool PRIO = AG_HOT_PRIO && TRANSFER == kTransferPqHi;    // (the compact PQ form measured 1.5 % SLOWER with it: only the default form carries it)
     if constexpr (PRIO) __builtin_amdgcn_s_setprio(3);
-    PqTableFill<AG_HOT444_BLOCK> tfill;
+    PqTableFill<BLOCK> tfill;
     if constexpr (LATE) tfill.load((int)threadIdx.x); else pq_prologue<TRANSFER>();
 
     const int wave = wave_in_block();
@@ -1732,7 +1752,7 @@ __global__ __launch_bounds__(AG_HOT444_BLOCK) AG_F32_SGPRS void write_rgb32_ycbc
     if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
     if constexpr (LATE) {
         tfill.store((int)threadIdx.x);
-        pq_table_barrier();
+        pq_table_barrier<BLOCK>();
     }
     for (uint32_t sidx = blockIdx.x * WPB + wave; sidx < total; sidx += step) {
         const uint32_t r = sidx / spans_per_row;
@@ -1878,7 +1898,7 @@ __global__ __launch_bounds__(AG_F32_STREAM_BLOCK) AG_F32_SGPRS void write_rgb32_
     if constexpr (AG_SUB_PRIO && !OUTREF) __builtin_amdgcn_s_setprio(0);
     if constexpr (LATE) {
         tfill.store((int)threadIdx.x);
-        pq_table_barrier();
+        pq_table_barrier<AG_F32_STREAM_BLOCK>();
     }
     for (uint32_t sidx = blockIdx.x * kF32Waves + wave; sidx < total; sidx += step) {
         const uint32_t r = sidx / spans_per_row;
@@ -2009,7 +2029,7 @@ __global__ __launch_bounds__(AG_F32_STREAM_BLOCK) AG_F32_SGPRS void write_rgb32_
     if constexpr (AG_SUB_PRIO) __builtin_amdgcn_s_setprio(0);
     if constexpr (LATE) {
         tfill.store((int)threadIdx.x);
-        pq_table_barrier();
+        pq_table_barrier<AG_F32_STREAM_BLOCK>();
     }
     for (uint32_t it = 0, sidx = span_of(0); sidx < total; sidx = span_of(++it)) {
         const uint32_t gy = sidx / spans_per_row;
@@ -2200,7 +2220,7 @@ __global__ __launch_bounds__(AG_RGBA_STREAM_BLOCK) AG_F32_SGPRS void write_rgba3
     if constexpr (AG_RGBA_PRIO) __builtin_amdgcn_s_setprio(0);
     if constexpr (LATE) {
         tfill.store((int)threadIdx.x);
-        pq_table_barrier();
+        pq_table_barrier<AG_RGBA_STREAM_BLOCK>();
     }
     for (uint32_t sidx = blockIdx.x * kRgbaWaves + wave; sidx < total; sidx += step) {
         const uint32_t r = sidx / spans_per_row;
@@ -2284,7 +2304,7 @@ __global__ __launch_bounds__(AG_RGBA_STREAM_BLOCK) AG_F32_SGPRS void write_rgba3
     if constexpr (AG_RGBA_PRIO) __builtin_amdgcn_s_setprio(0);
     if constexpr (LATE) {
         tfill.store((int)threadIdx.x);
-        pq_table_barrier();
+        pq_table_barrier<AG_RGBA_STREAM_BLOCK>();
     }
     for (uint32_t sidx = blockIdx.x * kRgbaWaves + wave; sidx < total; sidx += step) {
         const uint32_t gy = sidx / spans_per_row;
@@ -3229,7 +3249,7 @@ __global__ __launch_bounds__(AG_F32_REF_BLOCK) AG_F32_SGPRS void write_f32_ref_s
     if constexpr (AG_REF_PRIO) __builtin_amdgcn_s_setprio(0);
     if constexpr (LATE) {
         tfill.store((int)threadIdx.x);
-        pq_table_barrier();
+        pq_table_barrier<AG_F32_REF_BLOCK>();
     }
     for (uint32_t widx = blockIdx.x * kF32RefWaves + wave; widx < total; widx += step) {
         const uint32_t r = widx / chunks;
@@ -3289,11 +3309,11 @@ __global__ __launch_bounds__(AG_F32_REF_BLOCK) AG_F32_SGPRS void write_f32_ref_s
 // index of the two planes: 8 or 4 contiguous bytes per lane and plane, contiguous across the wave.  The row is a buffer resource
 // (no conditional load; a vector beyond the row reads zeros and its stores are clipped).  The generic kernel ran these at 0.70 of 8 TB/s.
 template <int DEPTH, int TRANSFER>
-__global__ __launch_bounds__(AG_F32_REF_BLOCK) void write_ga_stream(const WriteParams p)
+__global__ __launch_bounds__(AG_GA_BLOCK) void write_ga_stream(const WriteParams p)
 {
     static_assert(DEPTH == 16 || DEPTH == 32, "u16 or f32 samples");
     constexpr bool LATE = AG_PQ_LATE_FILL && DEPTH == 32 && TRANSFER == kTransferPqHi;
-    PqTableFill<AG_F32_REF_BLOCK> tfill;
+    PqTableFill<AG_GA_BLOCK> tfill;
     if constexpr (LATE) tfill.load((int)threadIdx.x); else if constexpr (DEPTH == 32) pq_prologue<TRANSFER>();
     constexpr int K = 4;
     constexpr int PXV = DEPTH == 16 ? 4 : 2;                            // pixels per 16-byte vector
@@ -3302,7 +3322,7 @@ __global__ __launch_bounds__(AG_F32_REF_BLOCK) void write_ga_stream(const WriteP
     const uint32_t nv = (uint32_t)p.width / PXV;                        // vectors per row (host: width % PXV == 0)
     const uint32_t chunks = (nv + 64 * K - 1) / (64 * K);
     const uint32_t total = chunks * (uint32_t)p.nrows;
-    const uint32_t step = gridDim.x * kF32RefWaves;
+    const uint32_t step = gridDim.x * kGaWaves;
     f32x4 v[K];
     auto issue = [&](uint32_t w) {
         const uint32_t r = w / chunks;
@@ -3312,12 +3332,12 @@ __global__ __launch_bounds__(AG_F32_REF_BLOCK) void write_ga_stream(const WriteP
 #pragma unroll
         for (int k = 0; k < K; ++k) v[k] = span_load16<true>(rs, vo, 1024u * k);
     };
-    issue(blockIdx.x * kF32RefWaves + wave);
+    issue(blockIdx.x * kGaWaves + wave);
     if constexpr (LATE) {
         tfill.store((int)threadIdx.x);
-        pq_table_barrier();
+        pq_table_barrier<AG_GA_BLOCK>();
     }
-    for (uint32_t widx = blockIdx.x * kF32RefWaves + wave; widx < total; widx += step) {
+    for (uint32_t widx = blockIdx.x * kGaWaves + wave; widx < total; widx += step) {
         const uint32_t r = widx / chunks;
         const uint32_t c = widx - r * chunks;
         const uint32_t row_bytes = (uint32_t)p.width * 2u;             // of a u16 plane row
@@ -3514,8 +3534,8 @@ static inline int grid_icc(long long threads_needed, char* label)
     return grid_capped(threads_needed, AG_ICC_BLOCK_CAP < AG_WRITE_BLOCK_CAP ? AG_ICC_BLOCK_CAP : AG_WRITE_BLOCK_CAP, label);
 }
 
-// A workgroup of the generic kernel that evaluates PQ in its close form starts by copying the 4-KiB exponent table to LDS: at one footprint
-// group per workgroup that is 4 KiB of LDS fill per 6 KiB of pixels for a gray f32 document.  A capped grid lets a workgroup run several
+// A workgroup of the generic kernel that evaluates PQ in its close form starts by copying the exponent table to LDS (2 KiB; 4 KiB when
+// the figures below were taken): at one footprint group per workgroup that was 4 KiB of LDS fill per 6 KiB of pixels for a gray f32 document.  A capped grid lets a workgroup run several
 // groups per copy: Gray32 -> 10-bit PQ at 8192^2 on fresh data 0.528 of 8 TB/s uncapped (65 536 blocks), 0.623 at 8192 or 16 384 blocks,
 // 0.59 at 32 768 (round 5; the streaming kernels, whose waves own 6-12 KiB each, prefer one span per wave: profiles/r05/prefetch_pipeline_ab.txt).
 #ifndef AG_PQ_TABLE_BLOCK_CAP
@@ -3816,11 +3836,11 @@ hipError_t launch_stream_int(const WriteParams& p, int depth, int planes, bool d
         const long long waves = (((long long)p.width / 4 + 255) / 256) * p.nrows;
         if (waves == 0) return hipSuccess;
         if (waves + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            const long long need = (waves + kF32RefWaves - 1) / kF32RefWaves;
-            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / kF32RefWaves, variant);
+            const long long need = (waves + kGaWaves - 1) / kGaWaves;
+            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / kGaWaves, variant);
             snprintf(label, kLabelBytes, "write_ga_stream<depth=16>");
-            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / kF32RefWaves);
-            hipLaunchKernelGGL((write_ga_stream<16, AVIFGPU_TRANSFER_CLIP>), dim3((int)blocks), dim3(AG_F32_REF_BLOCK), 0, st, p);
+            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / kGaWaves);
+            hipLaunchKernelGGL((write_ga_stream<16, AVIFGPU_TRANSFER_CLIP>), dim3((int)blocks), dim3(AG_GA_BLOCK), 0, st, p);
             return hipGetLastError();
         }
     }
@@ -3988,15 +4008,15 @@ hipError_t launch_stream_f32_sub_rgba(const WriteParams& p, int depth, int plane
         const long long waves = (((long long)p.width / 2 + 255) / 256) * p.nrows;
         if (waves == 0) return hipSuccess;
         if (waves + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            const long long need = (waves + kF32RefWaves - 1) / kF32RefWaves;
-            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / kF32RefWaves, variant);
+            const long long need = (waves + kGaWaves - 1) / kGaWaves;
+            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / kGaWaves, variant);
             snprintf(label, kLabelBytes, "write_ga_stream<depth=32,transfer=%d>", p.transfer);
-            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / kF32RefWaves);
+            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / kGaWaves);
             if (p.transfer == AVIFGPU_TRANSFER_PQ) {
-                if (pq_hi_launch(p)) hipLaunchKernelGGL((write_ga_stream<32, kTransferPqHi>), dim3((int)blocks), dim3(AG_F32_REF_BLOCK), 0, st, p);
-                else hipLaunchKernelGGL((write_ga_stream<32, AVIFGPU_TRANSFER_PQ>), dim3((int)blocks), dim3(AG_F32_REF_BLOCK), 0, st, p);
+                if (pq_hi_launch(p)) hipLaunchKernelGGL((write_ga_stream<32, kTransferPqHi>), dim3((int)blocks), dim3(AG_GA_BLOCK), 0, st, p);
+                else hipLaunchKernelGGL((write_ga_stream<32, AVIFGPU_TRANSFER_PQ>), dim3((int)blocks), dim3(AG_GA_BLOCK), 0, st, p);
             } else {
-                hipLaunchKernelGGL((write_ga_stream<32, AVIFGPU_TRANSFER_CLIP>), dim3((int)blocks), dim3(AG_F32_REF_BLOCK), 0, st, p);   // (gray saves: PQ or Clip, avifgpu_api.hip)
+                hipLaunchKernelGGL((write_ga_stream<32, AVIFGPU_TRANSFER_CLIP>), dim3((int)blocks), dim3(AG_GA_BLOCK), 0, st, p);   // (gray saves: PQ or Clip, avifgpu_api.hip)
             }
             return hipGetLastError();
         }
@@ -4128,7 +4148,7 @@ constexpr uint32_t kHistFlushTrips = 1u << 18;         // 2^18 trips x 1024 lane
 #ifndef AG_HIST_SPAN
 #define AG_HIST_SPAN 0
 #endif
-constexpr size_t kHistMaxTableLds = 40 * 1024;         // 16 KiB of bins + 4 KiB PQ table + this stay inside 64 KiB
+constexpr size_t kHistMaxTableLds = 40 * 1024;         // 16 KiB of bins + 2 KiB PQ table + this stay inside 64 KiB
 
 AG_DEV void hist_add(uint32_t* bins, uint32_t m, bool valid, int lane)
 {
@@ -4536,7 +4556,11 @@ static hipError_t launch_write_impl(const WriteParams& p, int depth, int planes,
             const long long spans = (long long)((p.width + span_px - 1) / span_px) * p.nrows;
             if (spans == 0) return hipSuccess;
             if (spans + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            constexpr int WPB = kHot444Waves;
+            // spans on 128-byte lines (a flat tile is one row): the two-wave workgroup; rows that start inside a line: the four-wave one
+            const uintptr_t bases = reinterpret_cast<uintptr_t>(p.src) | reinterpret_cast<uintptr_t>(p.dst[0]) | reinterpret_cast<uintptr_t>(p.dst[1]) | reinterpret_cast<uintptr_t>(p.dst[2]);
+            const uintptr_t strides = (uintptr_t)p.src_row_bytes | (uintptr_t)p.dst_stride[0] | (uintptr_t)p.dst_stride[1] | (uintptr_t)p.dst_stride[2];
+            const bool lines = (bases & 127) == 0 && (p.nrows == 1 || (strides & 127) == 0);
+            const int WPB = (lines ? AG_HOT444_BLOCK_LINES : AG_HOT444_BLOCK) / 64;
             const long long need = (spans + WPB - 1) / WPB;
             const long long cap = 256LL * 512 * 4 / WPB;                                      // 8192^2: one span per wave measured 5-6 % faster than two
             const long long blocks = capped_blocks(need, cap, variant);
@@ -4550,7 +4574,8 @@ static hipError_t launch_write_impl(const WriteParams& p, int depth, int planes,
 #else
             constexpr size_t lds_pad = 0;
 #endif
-#define AG_HOT3(TR, PX, NT_) hipLaunchKernelGGL((write_rgb32_ycbcr444_hot<TR, PX, NT_>), dim3((int)blocks), dim3(AG_HOT444_BLOCK), lds_pad, st, p)
+#define AG_HOT3(TR, PX, NT_) do { if (lines) hipLaunchKernelGGL((write_rgb32_ycbcr444_hot<TR, PX, NT_, AG_HOT444_BLOCK_LINES>), dim3((int)blocks), dim3(AG_HOT444_BLOCK_LINES), lds_pad, st, p); \
+                                  else hipLaunchKernelGGL((write_rgb32_ycbcr444_hot<TR, PX, NT_, AG_HOT444_BLOCK>), dim3((int)blocks), dim3(AG_HOT444_BLOCK), lds_pad, st, p); } while (0)
 #define AG_HOT2(TR, PX) do { if (nt) AG_HOT3(TR, PX, true); else AG_HOT3(TR, PX, false); } while (0)
 #define AG_HOT1(TR) do { if (px8) AG_HOT2(TR, 8); else AG_HOT2(TR, 4); } while (0)
             switch (p.transfer) {
