@@ -164,7 +164,7 @@ void release_device_caches()
     release_icc_tables();
 }
 
-int fill_write_params(const avifgpu_write_desc* d, int row0, int nrows, const WriteGeom& g, const IccArgs& icc, WriteParams& p)
+int fill_write_params(const avifgpu_write_desc* d, int row0, int nrows, const WriteGeom&, const IccArgs& icc, WriteParams& p)
 {
     memset(&p, 0, sizeof(p));
     if (const int rc = fill_icc_params(d, icc, p)) return rc;     // icc_tables.cpp: the ICC stage, its device tables included
@@ -205,7 +205,6 @@ int fill_write_params(const avifgpu_write_desc* d, int row0, int nrows, const Wr
             return fail(AVIFGPU_formatBadParameters, "luma coefficients %g %g %g are not a convex combination: the unclipped luma of the streaming kernels does not apply",
                         (double)p.my[0], (double)p.my[1], (double)p.my[2]);
     }
-    (void)g;
     return 0;
 }
 

@@ -293,11 +293,7 @@ AG_DEV f32x2 fast_linear_to_pq01_2_hi(f32x2 value, float mult)
     const f32x2 e2 = kPqM2 * f32x2{ nat_log2(q.x), nat_log2(q.y) };
     return f32x2{ nat_exp2_sat(e2.x), nat_exp2_sat(e2.y) };
 }
-// Build-time override of the per-launch choice (WriteParams::pq_close): 0 = the compact form everywhere, 2 = the close form
-// everywhere, 1 = as the descriptor says (AUTO = the close form at every depth since round 4).
-#ifndef AG_PQ_HI
-#define AG_PQ_HI 1
-#endif
+// (which form a launch takes -- WriteParams::pq_close, AG_PQ_HI -- is the launcher's choice: write_dispatch.h)
 
 // PQToLinear, reference ColorTransfer.cpp:94-117.  mult = 10000 / peak.
 //

@@ -2,6 +2,8 @@
 // Host-side validation and coefficient derivation live in avifgpu_api.hip and icc_tables.cpp; the kernels trust these.
 #pragma once
 #include <stdint.h>
+#include <stdio.h>
+#include <string.h>
 
 namespace avifgpu {
 
@@ -11,9 +13,29 @@ namespace avifgpu {
 //   (launch_write: contiguous 4:4:4 / interleaved tiles are launched as one long row), bit5 (32) no v_dot2 in the packed 8-bit ICC stage, bit6 (64) sampled ICC curves looked up in memory instead of interpolated in LDS, bit7 (128) IEEE division in the read kernels whatever the divisor,
 //   bits 8.. = block cap of EVERY capped launch (streaming kernels, write_px, read_px, write_hist_px): the grid is min(blocks of a one-trip
 //   launch, the launcher's compile-time cap, this number) -- it lowers a grid, never raises it; the label gains " cap=N/M" when it did
-//   (capped_blocks / label_cap, staging.h; tests/test_zz_gpu_grid_stride.py walks every grid-stride loop several times with it).  0 = none.
+//   (capped_blocks / label_cap below; tests/test_zz_gpu_grid_stride.py walks every grid-stride loop several times with it).  0 = none.
 //   Code that reads the word as a switch looks at its low byte only.  (Bits 3 and 4 selected a register-prefetch and an XCD-contiguous variant in round 1; both lost and were removed.)
 enum : int { kHotDefault = 1 | 2 | 4 };
+
+constexpr int kLabelBytes = 192;                    // kernel label buffers handed to launch_*()
+
+// Workgroups of a capped launch: `need` = those of a launch in which every wave makes one trip of its grid-stride loop, `cap` = the
+// launcher's own compile-time cap.  Bits 8.. of the tuning word (kernel_params.h) lower the grid further and never raise it: with them
+// the tests make every wave take several trips on a tile of a few thousand pixels.  Zero there: exactly min(need, cap).
+inline long long capped_blocks(long long need, long long cap, int word)
+{
+    long long blocks = need < cap ? need : cap;
+    const long long asked = (long long)(word >> 8);
+    if (asked > 0 && asked < blocks) blocks = asked;
+    return blocks < 1 ? 1 : blocks;
+}
+// The launch label says so when the word lowered the grid: " cap=N/M", N workgroups launched where one trip per wave takes M.
+inline void label_cap(char* label, long long launched, long long need, long long cap)
+{
+    if (launched >= need || launched >= cap || strstr(label, " cap=") != nullptr) return;
+    const size_t n = strlen(label);
+    if (n < (size_t)kLabelBytes) snprintf(label + n, kLabelBytes - n, " cap=%lld/%lld", launched, need);
+}
 
 // Cache policy of the K 16-byte loads a wave issues per span in the RGB f32 streaming kernels (and in their math-free twin,
 // pattern_probe.hip).  Round 4 sent the first and the last load of a span through the L2 / Infinity Cache normally (= 1), so that a

@@ -34,8 +34,6 @@ struct IccArgs {
 // host pointers, checked with check_grid_tiles of grid_save.h by whoever builds it: avifgpu_write_rows_grid, the shim) instead of dst[] / dst_stride[], which are then ignored.
 struct GridDest { avifgpu_grid grid; const avifgpu_grid_tile* tiles; };
 
-constexpr int kLabelBytes = 192;                    // kernel label buffers handed to launch_*()
-
 struct WriteGeom { bool color, alpha, dst16; int xs, ys, nplanes; };
 struct ReadGeom { int xs, ys, nch, transfer; bool alpha; };
 
@@ -67,24 +65,6 @@ void read_plane_extent(const avifgpu_read_desc* d, const ReadGeom& g, int plane,
 bool read_plane_used(const avifgpu_read_desc* d, const ReadGeom& g, int plane);
 
 int  hot_variant();
-// Workgroups of a capped launch: `need` = those of a launch in which every wave makes one trip of its grid-stride loop, `cap` = the
-// launcher's own compile-time cap.  Bits 8.. of the tuning word (kernel_params.h) lower the grid further and never raise it: with them
-// the tests make every wave take several trips on a tile of a few thousand pixels.  Zero there: exactly min(need, cap).
-inline long long capped_blocks(long long need, long long cap, int word)
-{
-    long long blocks = need < cap ? need : cap;
-    const long long asked = (long long)(word >> 8);
-    if (asked > 0 && asked < blocks) blocks = asked;
-    return blocks < 1 ? 1 : blocks;
-}
-// The launch label says so when the word lowered the grid: " cap=N/M", N workgroups launched where one trip per wave takes M.
-inline void label_cap(char* label, long long launched, long long need, long long cap)
-{
-    if (launched >= need || launched >= cap || strstr(label, " cap=") != nullptr) return;
-    const size_t n = strlen(label);
-    if (n < (size_t)kLabelBytes) snprintf(label + n, kLabelBytes - n, " cap=%lld/%lld", launched, need);
-}
-
 // ---- save_stats.cpp: the three statistics a save can carry -- the code histogram (avifgpu_histogram_attach), the thumbnail sums
 // (avifgpu_thumbnail_attach), the summary of the written planes (avifgpu_summary_attach) -- armed, checked and launched in one place ------
 // What is armed for one write call and where it goes.  A null target: not armed, or (the histogram) the descriptor is not counted.

@@ -22,6 +22,7 @@
 #include <type_traits>
 #include "kernel_params.h"
 #include "staging.h"
+#include "write_dispatch.h"
 #include "device_math.h"
 #include "satword_f32.h"
 #include "icc_pipeline32.h"
@@ -32,7 +33,7 @@
 namespace avifgpu {
 
 // ---- code objects (round 5) ---------------------------------------------------------------------------------------------------
-// The library's Makefile compiles this file EIGHT times, each time with another -DAG_WRITE_PART, into eight code objects that the HIP
+// The library's Makefile compiles this file TEN times, each time with another -DAG_WRITE_PART, into ten code objects that the HIP
 // runtime loads one by one, on the first launch of a kernel of theirs -- a save then pays for the object its kernels live in, not for
 // all 650 instantiations (round 4: one 6.8-MB object, 18 ms in front of the first launch of a process):
 //    1   launch_write(), the only entry point, + the RGB f32 4:4:4 streaming kernels (the headline, with and without a profile in front) and
@@ -47,18 +48,16 @@ namespace avifgpu {
 //    0   everything in one object (tools/ab_variants.sh builds its A/B libraries that way).
 // A kernel is emitted where a launch of it is instantiated; the launchers of a part are compiled in that part only (kHere* below), the
 // streaming part reaches the others through the four launch_planes_* functions.
-#ifndef AG_WRITE_PART
-#define AG_WRITE_PART 0
-#endif
+// (AG_WRITE_PART defaults to 0 in write_dispatch.h, which decides with it where write_px's workgroup size depends on the part)
 constexpr bool kHerePlain  = AG_WRITE_PART != 36 && AG_WRITE_PART != 38 && AG_WRITE_PART != 1;     // write_px without icc = 6 / 8 (of the depth of the part)
 constexpr bool kHereIcc6   = AG_WRITE_PART == 0 || AG_WRITE_PART == 36;
 constexpr bool kHereIcc8   = AG_WRITE_PART == 0 || AG_WRITE_PART == 38;
-hipError_t launch_planes_d8(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, hipStream_t st, char* label);
-hipError_t launch_planes_d16(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, hipStream_t st, char* label);
-hipError_t launch_planes_d32(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, hipStream_t st, char* label);
-hipError_t launch_planes_d32_rgb(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, hipStream_t st, char* label);
-hipError_t launch_planes_d32_icc6(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, hipStream_t st, char* label);
-hipError_t launch_planes_d32_icc8(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, hipStream_t st, char* label);
+hipError_t launch_planes_d8(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, const WriteLaunch& L, hipStream_t st);
+hipError_t launch_planes_d16(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, const WriteLaunch& L, hipStream_t st);
+hipError_t launch_planes_d32(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, const WriteLaunch& L, hipStream_t st);
+hipError_t launch_planes_d32_rgb(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, const WriteLaunch& L, hipStream_t st);
+hipError_t launch_planes_d32_icc6(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, const WriteLaunch& L, hipStream_t st);
+hipError_t launch_planes_d32_icc8(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, const WriteLaunch& L, hipStream_t st);
 
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 #ifndef AG_ICC_F32
@@ -66,9 +65,6 @@ typedef float f32x4_t __attribute__((ext_vector_type(4)));
 #endif
 #ifndef AG_ICC4_F32
 #define AG_ICC4_F32 1
-#endif
-#ifndef AG_ICC1_HOT
-#define AG_ICC1_HOT 1
 #endif
 #ifndef AG_ICC_MATRIX_F32
 #define AG_ICC_MATRIX_F32 1      /* with the single-precision curves: the 3x3 in fp32 FMAs as well (-6 %, same exact-match rate) */
@@ -84,8 +80,7 @@ template <int ICC> struct IccF32 { static constexpr bool value = (ICC == 2 && AG
 // form at build time for A/B.
 // The PQ functions return pq in [0, 1] (clamped inside their last v_exp_f32, NaN -> 0), so pq * maxValue needs no clamp; the other
 // curves keep the v_med3_f32 (which returns 0 for the quiet NaN a v_mul_f32 / v_log_f32 makes of any NaN input).
-constexpr int kTransferPqHi = 4;
-static inline bool pq_hi_launch(const WriteParams& p) { return AG_PQ_HI == 2 || (AG_PQ_HI == 1 && p.pq_close); }
+// (kTransferPqHi = 4 and pq_hi_launch: write_dispatch.h)
 template <int TRANSFER> constexpr bool is_pq() { return TRANSFER == AVIFGPU_TRANSFER_PQ || TRANSFER == kTransferPqHi; }
 
 // scaled, clamped, not yet truncated: in [0, maxValue]
@@ -220,9 +215,6 @@ struct IccPowTableF { const f32x4_t* t; };          // LDS, 128 entries of {c, L
 // transfer curve barely see: exact-match rate against the real lcms2 0.99889 -> 0.99868 (parametric document curves -> PQ) and
 // 0.99985 -> 0.99982 (-> sRGB, 12-bit Clip), bars 0.99 / 0.985 -- for 3.5x less arithmetic per pow (icc=4 0.44 -> 0.75 of
 // 8 TB/s, icc=2 0.43 -> 0.56; profiles/r02/icc_f32_ab.txt).  0 selects the double-float evaluation below (float-ulp accurate).
-#ifndef AG_ICC_FASTPOW
-#define AG_ICC_FASTPOW 1
-#endif
 AG_DEV float icc_pow32(const IccPowTableF& T, float x, float gh, float gl)
 {
 #if AG_ICC_FASTPOW
@@ -328,9 +320,6 @@ AG_DEV void icc_trc_simple4(const IccSimple& q, f32x4_t& v)
     const f32x2 a = icc_trc_simple2(q, f32x2{ v.x, v.y }), b = icc_trc_simple2(q, f32x2{ v.z, v.w });
     v.x = a.x; v.y = a.y; v.z = b.x; v.w = b.y;
 }
-#ifndef AG_ICC2_HOT
-#define AG_ICC2_HOT 1
-#endif
 
 // The parametric variants read up to 43 double parameters per pixel.  As kernel arguments they live in SGPRs, more than the
 // scalar file holds next to everything else: the compiler spills them to VGPR lanes and reads them back with v_readlane_b32
@@ -791,13 +780,9 @@ AG_DEV uint32_t luma_code(const WriteParams& p, uint32_t r, uint32_t g, uint32_t
 }
 
 // ---- generic kernel ----------------------------------------------------------------------------
-enum { kOutRefColor = 0, kOutRefGray = 1, kOutYcbcr = 2 };
 
 #ifndef AG_W_PACK
 #define AG_W_PACK 2
-#endif
-#ifndef AG_W8_NC
-#define AG_W8_NC 8
 #endif
 #ifndef AG_W16TO8_FAST
 #define AG_W16TO8_FAST 1
@@ -807,12 +792,6 @@ enum { kOutRefColor = 0, kOutRefGray = 1, kOutYcbcr = 2 };
 #endif
 #ifndef AG_W8_PACKED
 #define AG_W8_PACKED 1
-#endif
-#ifndef AG_W16_NC
-#define AG_W16_NC 4        /* chroma samples per lane of the generic kernel into u16 planes (no ICC) */
-#endif
-#ifndef AG_W8_NC_ALPHA
-#define AG_W8_NC_ALPHA 4
 #endif
 #ifndef AG_W8_SPANLOAD
 #define AG_W8_SPANLOAD 0
@@ -839,32 +818,7 @@ template <int DEPTH, int PLANES, int OUT, bool DST16, bool ALIGNED, int ICC> con
 {
     return AG_W8_PACKED && AG_ICC8_FAST && ICC == 3 && DEPTH == 8 && (PLANES == 3 || PLANES == 4) && OUT == 2 /* kOutYcbcr */ && !DST16 && ALIGNED;
 }
-// chroma samples per lane: 4 for u16 planes, AG_W8_NC for u8 planes (every plane store >= 8 / 4 bytes per lane)
-// The parametric ICC variants (2, 4) carry ~300 instructions and up to 86 parameter VGPRs per pixel stream: with sub-sampled chroma
-// 2 chroma samples per lane keep a 4:2:0 footprint at 8 pixels (16: 197 VGPRs, 2 waves/SIMD, 6.9 k instructions; measured
-// 0.412 -> 0.370 ms).  4:4:4 keeps 4 pixels per lane (2 measured slower: 0.487 -> 0.507 ms, narrower loads and stores).
-#ifndef AG_ICC_TAB_NC2
-#define AG_ICC_TAB_NC2 0        /* 1 = the table-driven ICC stages (5, 7) with sub-sampled chroma: 2 chroma samples per lane (A/B hook) */
-#endif
-template <bool DST16, int PLANES, int XS, int ICC = 0> struct WriteShape {
-    // ICC == 5 (the 16-bit table transform) saved to u8 planes: 4 chroma samples per lane like the u16 layouts.  With 8, a 4:2:0 footprint
-    // is 32 pixels x two 16-byte gathers each, all hoisted: 315 VGPRs = ONE wave per SIMD (profiles/r02/isa/resources.tsv); with 4 it is
-    // 16 pixels and the kernel fits 3-4 waves.
-    static constexpr int NC = ((ICC == 2 || ICC == 4 || ICC == 8 || ((ICC == 5 || ICC == 7) && AG_ICC_TAB_NC2)) && XS == 1) ? 2 : ((DST16 && ICC == 0) ? AG_W16_NC : ((DST16 || ICC == 5 || ICC == 7) ? 4 : ((PLANES == 2 || PLANES == 4) ? AG_W8_NC_ALPHA : AG_W8_NC)));
-    static constexpr int PXT = NC << XS;
-};
-
-// Workgroup size of the generic write kernel (its waves share only the per-workgroup tables).
-// Round 5, fresh data (profiles/r05/read_samples_per_lane_fresh_data.txt, block 5): 256 threads stand for every generic kernel (128: 0...-20 %,
-// 512: -1...-9 %) except the sampled-curve profile kernel (icc = 6, a code object of its own: part 36), whose workgroups copy up to 48 KiB of
-// curve tables to LDS -- 512 threads halve the copies per pixel: 0.437 -> 0.384 ms at 8192^2 (+14 %).
-#ifndef AG_WPX_BLOCK
-#if AG_WRITE_PART == 36
-#define AG_WPX_BLOCK 512
-#else
-#define AG_WPX_BLOCK 256
-#endif
-#endif
+// (WriteShape -- the chroma samples and pixels a thread of write_px owns -- and AG_WPX_BLOCK, its workgroup: write_dispatch.h)
 constexpr int kWpxWaves = AG_WPX_BLOCK / 64;
 template <int DEPTH, int PLANES, int OUT, bool DST16, int XS, int YS, int TRANSFER, bool ALIGNED, int ICC = 0>
 __global__ __launch_bounds__(AG_WPX_BLOCK) void write_px(const WriteParams p)
@@ -1420,24 +1374,14 @@ __global__ __launch_bounds__(AG_WPX_BLOCK) void write_px(const WriteParams p)
 // Workgroup size of the streaming kernels.  Their waves share nothing (private LDS strips, no barrier), so the workgroup is only a
 // scheduling unit -- and a small one fills the CUs more evenly: C4 8192^2 0.2015 ms with 256 threads, 0.1940 with 128, 0.1936 with
 // 64, 0.2015 / 0.2007 with 512 / 1024 (two runs each, profiles/r02/stream_block_size.txt).  128 halves the number of dispatches of 64.
-#ifndef AG_STREAM_BLOCK
-#define AG_STREAM_BLOCK 128
-#endif
-constexpr int kStreamWaves = AG_STREAM_BLOCK / 64;
+// (AG_STREAM_BLOCK = 128: write_dispatch.h)
 // The interleaved f32 hand-off (write_f32_ref_stream) and gray + alpha (write_ga_stream) went to 256 in round 5: on fresh data 0.782-0.789 ->
 // 0.796-0.801 of 8 TB/s at 8192^2 with nothing else moved (profiles/r05/workgroup_size_fresh_data_ab.txt; the 16-bit kernels and the
 // integer hand-off are indifferent and stay at 128).  With the 2-KiB PQ exponent table (device_math.h) the hand-off runs from ONE wave:
 // it copies the table with two loads and two LDS writes and waits for nobody (pq_table_barrier<64> is a fence).  Measured on two boxes
 // (profiles/pq_half_table/): the four-wave workgroup LOST 1.5-3 % on the hand-off rows with the smaller table (128 threads the same),
 // the single wave is level with or ahead of the 4-KiB parent on every row (16384^2 hand-off +4 %).  write_ga_stream keeps its 256.
-#ifndef AG_F32_REF_BLOCK
-#define AG_F32_REF_BLOCK 64
-#endif
-#ifndef AG_GA_BLOCK
-#define AG_GA_BLOCK 256
-#endif
-constexpr int kGaWaves = AG_GA_BLOCK / 64;
-constexpr int kF32RefWaves = AG_F32_REF_BLOCK / 64;
+// (AG_F32_REF_BLOCK = 64, AG_GA_BLOCK = 256: write_dispatch.h)
 
 typedef float    f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -1510,10 +1454,7 @@ AG_DEV int wave_in_block() { return __builtin_amdgcn_readfirstlane((int)(threadI
 
 // Workgroup size of the RGB f32 streaming kernels (round 4): four waves share one copy of the PQ exponent table, and with the
 // half-span strips below a workgroup needs 16 KiB of LDS -- 8 waves per SIMD again (profiles/r04/occupancy_ab.txt).
-#ifndef AG_F32_STREAM_BLOCK
-#define AG_F32_STREAM_BLOCK 256
-#endif
-constexpr int kF32Waves = AG_F32_STREAM_BLOCK / 64;
+// (AG_F32_STREAM_BLOCK = 256: write_dispatch.h)
 
 // Transfer-major -> lane-major transpose of a wave's span of 64 K float4 (lane l loaded float4 number 64 k + l; it wants numbers
 // K l ... K l + K - 1: its PXL pixels) through a wave-private strip of HALF a span (32 K float4 = 3 KiB for K = 6): the first K / 2
@@ -1641,12 +1582,6 @@ template <bool NT, typename V> AG_DEV void stream_store(V* p, V v)
 #ifndef AG_F32_SGPRS
 #define AG_F32_SGPRS
 #endif
-#ifndef AG_SUB_SPW2
-#define AG_SUB_SPW2 1                  /* 4:2:2 tiles of whole 512-pixel spans: two spans per wave (write_rgb32_ycbcr_sub_hot's loop) */
-#endif
-#ifndef AG_SUB_SPW2_MIN_SPANS
-#define AG_SUB_SPW2_MIN_SPANS 32768
-#endif
 #ifndef AG_RGBA_PRIO
 #define AG_RGBA_PRIO 0
 #endif
@@ -1678,12 +1613,7 @@ template <bool NT, typename V> AG_DEV void stream_store(V* p, V v)
 //    Neighbouring spans then SHARE the line their border falls in, and the smaller the workgroup, the more of those borders lie between
 //    workgroups -- on other CUs, other XCDs, other L2s: 6001 x 4001 measured -5 % at 128 threads and -8 % at 64.
 // AG_HOT444_GLOBAL (A/B, off): whole spans addressed with 64-bit lane pointers (the ragged last span of a row keeps the buffer form).
-#ifndef AG_HOT444_BLOCK
-#define AG_HOT444_BLOCK AG_F32_STREAM_BLOCK
-#endif
-#ifndef AG_HOT444_BLOCK_LINES
-#define AG_HOT444_BLOCK_LINES 128
-#endif
+// (both defaults: write_dispatch.h)
 #ifndef AG_MEASURE
 #define AG_MEASURE 0          /* 1: measuring knobs that read the environment (AVIFGPU_DEBUG_LDS_PAD) are compiled in */
 #endif
@@ -2131,14 +2061,8 @@ __global__ __launch_bounds__(AG_F32_STREAM_BLOCK) AG_F32_SGPRS void write_rgb32_
 // non-temporal wave-loads.  Alpha clamp / premultiply / curve per pixel as loaded; the four levels of a pixel (integer-valued
 // floats, oetf_level2; round 3 packed u16 codes) go to the wave-private strip as one 16-byte write, then lane l reads back pixels
 // [4l, 4l+4) (span_transpose: half a span at a time, 2 KiB of LDS per wave) and writes 8 contiguous bytes per plane, non-temporal.
-#ifndef AG_RGBA_HOT_PXL
-#define AG_RGBA_HOT_PXL 4
-#endif
 // 256-thread workgroups for this one: 16384^2 0.997 -> 0.977 ms (the three-plane kernels prefer 128, profiles/r02/stream_block_size.txt)
-#ifndef AG_RGBA_STREAM_BLOCK
-#define AG_RGBA_STREAM_BLOCK 256
-#endif
-constexpr int kRgbaWaves = AG_RGBA_STREAM_BLOCK / 64;
+// (AG_RGBA_STREAM_BLOCK = 256: write_dispatch.h)
 // Stage A of a lane's PXL RGBA pixels as loaded (one float4 each): [ICC curve / matrix,] alpha clamp, premultiply, transfer curve;
 // v[k] becomes { R, G, B, A } as LEVELS (integer-valued floats, oetf_level2).  WriteHeifImage.cpp:1040-1096.
 template <int TRANSFER, int ICCV, int PXL>
@@ -2379,9 +2303,6 @@ __global__ __launch_bounds__(AG_RGBA_STREAM_BLOCK) AG_F32_SGPRS void write_rgba3
 // write_rgb32_ycbcr444_hot<.., 8, ..>: ds_write_b128 at (64k + lane), read back pixel-major with 3 x ds_read_b128 at the
 // conflict-free 12-dword lane stride, 3x3 matrix, three 16-byte plane stores.  width % 8 == 0 keeps every row 16-byte aligned and
 // every lane either whole or idle.
-#ifndef AG_RGB16_NS
-#define AG_RGB16_NS 1      /* 2 and 4 measured 2-9 % slower on every geometry (profiles/r02/rgb16_streaming_geometry.txt) */
-#endif
 template <int NS, bool TO8 = false>      // spans per wave trip: all NS x 3 loads are issued before the first is consumed; TO8: u8 planes (see write_rgb16_ycbcr_sub_hot)
 __global__ __launch_bounds__(AG_STREAM_BLOCK) void write_rgb16_ycbcr444_hot(const WriteParams p)
 {
@@ -2822,12 +2743,6 @@ __global__ __launch_bounds__(AG_STREAM_BLOCK) void write_rgba16_ycbcra_sub_hot(c
 // in the oracle's order, v_floor_f32 + v_cvt_pk_u8_f32 straight into the lane's packed plane vectors.  Stores: 16 bytes per lane per
 // luma row, 8 (16 at 4:4:4) per chroma plane, contiguous across the wave, non-temporal.  Same bytes as the generic kernel
 // (tests/test_gpu_kernel_equivalence.py).  Widths that are multiples of 8, rows and planes dword-aligned; everything else stays generic.
-#ifndef AG_RGB8_HOT
-#define AG_RGB8_HOT 1
-#endif
-#ifndef AG_RGB8_16_WAVES
-#define AG_RGB8_16_WAVES 2         /* waves per workgroup of write_rgb8_ycbcr16_hot */
-#endif
 #ifndef AG_RGB8_FIRST_CACHED
 #define AG_RGB8_FIRST_CACHED 0     /* 1 = the first of a span's loads allocates; 0 = all non-temporal (equal or ahead on truly fresh data: kernel_params.h, AG_EDGE_CACHED) */
 #endif
@@ -3466,12 +3381,6 @@ __global__ __launch_bounds__(AG_STREAM_BLOCK) void write_int_ref_stream(const Wr
 // one-set loop), write_int_ref_stream at 0.71.  Here a wave owns 4 KiB of a row: four 1-KiB non-temporal buffer loads, four stores at the same
 // offsets, nothing else; a tile whose rows are contiguous on both sides is ONE row (the launcher).  Row bytes, pointers and strides dword-aligned.
 struct CopyParams { const uint8_t* src; uint8_t* dst; long long src_stride, dst_stride, row_bytes; int32_t nrows; };
-#ifndef AG_COPY_BLOCK
-#define AG_COPY_BLOCK 128
-#endif
-#ifndef AG_COPY_K
-#define AG_COPY_K 2               /* 16-byte vectors per lane and wave trip */
-#endif
 template <int K>
 __global__ __launch_bounds__(AG_COPY_BLOCK) void write_copy_rows_stream(const CopyParams c)
 {
@@ -3499,627 +3408,251 @@ __global__ __launch_bounds__(AG_COPY_BLOCK) void write_copy_rows_stream(const Co
 }
 
 // ---- dispatch --------------------------------------------------------------------------------------
-#ifndef AG_RGBA_BLOCK_CAP
-#define AG_RGBA_BLOCK_CAP (256LL * 512)       // C5 (1 M spans): 1.18 ms at 16k blocks, 1.01 at 64k, 0.99 at 128k, 1.01 at 256k
-#endif
-#ifndef AG_STREAM_BLOCK_CAP
-#define AG_STREAM_BLOCK_CAP (256LL * 512)     // grid cap of the streaming kernels (grid-stride beyond it); see AG_WRITE_BLOCK_CAP
-#endif
-#ifndef AG_WRITE_BLOCK_CAP
-#define AG_WRITE_BLOCK_CAP (256LL * 512)
-#endif
-// Workgroups of a write_px launch under the compile-time cap `cap` and the tuning word's (capped_blocks, staging.h); `label` is the
-// launch's finished label and gains " cap=N/M" when the word lowered the grid.
-static inline int grid_capped(long long threads_needed, long long cap, char* label)
+// Which kernel a save takes, on which grid and under which label is decided in write_dispatch.h (decide_write: no HIP call, held on the
+// CPU to the recorded choices by tools/write_dispatch_check.cpp).  What follows turns a decision into the instantiation: with_transfer,
+// with_bool and with_chroma make template arguments of its runtime values, and each code object holds the launches of its own kernels.
+// A kernel is emitted where a launch of it is instantiated: a helper below enumerates exactly the values its callers' kernels exist for.
+template <int V> using Int = std::integral_constant<int, V>;
+// f(Int<kernel-side transfer id>): the five curves of a 32-bit colour document
+template <class F> static inline void with_transfer(int tr, F&& f)
 {
-    const long long need = (threads_needed + AG_WPX_BLOCK - 1) / AG_WPX_BLOCK;
-    const long long blocks = capped_blocks(need, cap, hot_variant());
-    label_cap(label, blocks, need, cap);
-    return (int)blocks;
+    switch (tr) {
+    case kTransferPqHi:             f(Int<kTransferPqHi>()); break;
+    case AVIFGPU_TRANSFER_PQ:       f(Int<AVIFGPU_TRANSFER_PQ>()); break;
+    case AVIFGPU_TRANSFER_HLG:      f(Int<AVIFGPU_TRANSFER_HLG>()); break;
+    case AVIFGPU_TRANSFER_SMPTE428: f(Int<AVIFGPU_TRANSFER_SMPTE428>()); break;
+    default:                        f(Int<AVIFGPU_TRANSFER_CLIP>()); break;
+    }
 }
-static inline int grid_for(long long threads_needed, char* label)
+template <class F> static inline void with_bool(bool b, F&& f) { if (b) f(std::true_type()); else f(std::false_type()); }
+// f(Int<xs>, Int<ys>, nearest): 4:4:4 has one form, 4:2:2 and 4:2:0 one per chroma filter
+template <class F> static inline void with_chroma(int xs, int ys, bool nearest, F&& f)
 {
-    // 8192^2 frames are indifferent to 16k...128k blocks; 16384^2 frames are not (RGB16 -> 12-bit 4:4:4: 0.684 ms at 16k,
-    // 0.543 ms at 128k -- profiles/r01/ab_write_variants.txt): keep a wave's grid-stride loop short
-    return grid_capped(threads_needed, AG_WRITE_BLOCK_CAP, label);
+    if (xs == 0) f(Int<0>(), Int<0>(), std::false_type());
+    else if (ys == 0) with_bool(nearest, [&](auto nr) { f(Int<1>(), Int<0>(), nr); });
+    else with_bool(nearest, [&](auto nr) { f(Int<1>(), Int<1>(), nr); });
+}
+#define AG_V(x) decltype(x)::value
+
+// the aligned or the unaligned instantiation of write_px behind ICC stage `ICC`, on the decision's grid
+template <int DEPTH, int PLANES, int OUT, bool DST16, int XS, int YS, int TRANSFER, int ICC>
+static hipError_t launch_px(const WriteParams& p, const WriteLaunch& L, hipStream_t st)
+{
+    if (L.aligned) hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, true, ICC>), dim3((int)L.blocks), dim3(AG_WPX_BLOCK), L.lds, st, p);
+    else hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, false, ICC>), dim3((int)L.blocks), dim3(AG_WPX_BLOCK), L.lds, st, p);
+    return hipGetLastError();
 }
 
-// The parametric ICC variants set up ~60 wave-uniform parameters (and their pow table) per workgroup: a capped grid lets a wave
-// run several groups per set-up.
-#ifndef AG_ICC_BLOCK_CAP
-#define AG_ICC_BLOCK_CAP (256LL * 32)      /* 8192^2: 0.405 ms uncapped, 0.390 at 16k, 0.371 at 8k / 4k, 0.388 at 2k, 0.416 at 1k blocks (variant 2) */
-#endif
-static inline int grid_icc(long long threads_needed, char* label)
-{
-    return grid_capped(threads_needed, AG_ICC_BLOCK_CAP < AG_WRITE_BLOCK_CAP ? AG_ICC_BLOCK_CAP : AG_WRITE_BLOCK_CAP, label);
-}
-
-// A workgroup of the generic kernel that evaluates PQ in its close form starts by copying the exponent table to LDS (2 KiB; 4 KiB when
-// the figures below were taken): at one footprint group per workgroup that was 4 KiB of LDS fill per 6 KiB of pixels for a gray f32 document.  A capped grid lets a workgroup run several
-// groups per copy: Gray32 -> 10-bit PQ at 8192^2 on fresh data 0.528 of 8 TB/s uncapped (65 536 blocks), 0.623 at 8192 or 16 384 blocks,
-// 0.59 at 32 768 (round 5; the streaming kernels, whose waves own 6-12 KiB each, prefer one span per wave: profiles/r05/prefetch_pipeline_ab.txt).
-#ifndef AG_PQ_TABLE_BLOCK_CAP
-#define AG_PQ_TABLE_BLOCK_CAP (256LL * 32)
-#endif
-template <int TRANSFER>
-static inline int grid_px(long long threads_needed, char* label)
-{
-    return grid_capped(threads_needed, (TRANSFER == kTransferPqHi && AG_PQ_TABLE_BLOCK_CAP < AG_WRITE_BLOCK_CAP) ? AG_PQ_TABLE_BLOCK_CAP : AG_WRITE_BLOCK_CAP, label);
-}
-
+// the ICC stages a document of this depth can carry; the parts of 32-bit documents hold theirs only (kHere*)
 template <int DEPTH, int PLANES, int OUT, bool DST16, int XS, int YS, int TRANSFER>
-static hipError_t launch_one(const WriteParams& p, hipStream_t st, char* label)
+static hipError_t launch_one(const WriteParams& p, const WriteLaunch& L, hipStream_t st)
 {
-    constexpr int PXT = WriteShape<DST16, PLANES, XS>::PXT;
-    long long groups = (long long)((p.width + PXT - 1) / PXT) * ((p.nrows + (1 << YS) - 1) >> YS);
-    if (groups == 0) return hipSuccess;
-    if constexpr (DEPTH == 32 && PLANES >= 3) {
-        bool linear = true;
-        for (int c = 0; c < 3; ++c) linear = linear && p.icc_trc_linear[c] != 0;
-        if (p.icc_trc_type[0] != 0 && p.icc_s_tab == nullptr && (p.icc_out == 4 || !linear)) {      // variants 2 and 4 use a smaller footprint
-            constexpr int PXT2 = WriteShape<DST16, PLANES, XS, 2>::PXT;
-            groups = (long long)((p.width + PXT2 - 1) / PXT2) * ((p.nrows + (1 << YS) - 1) >> YS);
-        }
-    }
-    if (groups >= 0x7fffffffLL - 256LL * 65536) return hipErrorInvalidValue;   // 32-bit group index in the kernel
-    // every pointer and stride a multiple of 16 => the branch-free vector path
-    uintptr_t bits = reinterpret_cast<uintptr_t>(p.src) | (uintptr_t)p.src_row_bytes;
-    for (int pl = 0; pl < 4; ++pl) if (p.dst[pl]) bits |= reinterpret_cast<uintptr_t>(p.dst[pl]) | (uintptr_t)p.dst_stride[pl];
-    const bool aligned = (bits & 15) == 0;
-    snprintf(label, kLabelBytes, "write_px<depth=%d,planes=%d,out=%d,dst16=%d,xs=%d,ys=%d,transfer=%d,aligned=%d>",
-             DEPTH, PLANES, OUT, (int)DST16, XS, YS, TRANSFER, (int)aligned);
+    auto px = [&](auto icc) { return launch_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, AG_V(icc)>(p, L, st); };
     if constexpr (DEPTH == 8 && PLANES >= 3) {
-        if (p.icc8_s1 != nullptr) {                 // 8-bit matrix-shaper ICC transform requested
-            snprintf(label, kLabelBytes, "write_px<depth=%d,planes=%d,out=%d,dst16=%d,xs=%d,ys=%d,transfer=%d,aligned=%d,icc=3>",
-                     DEPTH, PLANES, OUT, (int)DST16, XS, YS, TRANSFER, (int)aligned);
-            const int blocks = grid_capped(groups, 2048 < AG_WRITE_BLOCK_CAP ? 2048 : AG_WRITE_BLOCK_CAP, label);     // tables are copied per block
-            if (aligned) hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, true, 3>), dim3(blocks), dim3(AG_WPX_BLOCK), 0, st, p);
-            else hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, false, 3>), dim3(blocks), dim3(AG_WPX_BLOCK), 0, st, p);
-            return hipGetLastError();
-        }
-    }
-    if constexpr (DEPTH == 8 && PLANES >= 3) {
-        if (p.icc16_clut != nullptr) {              // 8-bit document behind a LUT-based profile: the 33^3 table, evaluated like PrelinEval8 (round 6)
-            constexpr int PXT7 = WriteShape<DST16, PLANES, XS, 7>::PXT;
-            groups = (long long)((p.width + PXT7 - 1) / PXT7) * ((p.nrows + (1 << YS) - 1) >> YS);
-            snprintf(label, kLabelBytes, "write_px<depth=%d,planes=%d,out=%d,dst16=%d,xs=%d,ys=%d,transfer=%d,aligned=%d,icc=7>",
-                     DEPTH, PLANES, OUT, (int)DST16, XS, YS, TRANSFER, (int)aligned);
-            if (aligned) hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, true, 7>), dim3(grid_for(groups, label)), dim3(AG_WPX_BLOCK), 0, st, p);
-            else hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, false, 7>), dim3(grid_for(groups, label)), dim3(AG_WPX_BLOCK), 0, st, p);
-            return hipGetLastError();
-        }
+        if (L.icc == 3) return px(Int<3>());            // the 8-bit matrix-shaper
+        if (L.icc == 7) return px(Int<7>());            // a LUT-based profile: the 33^3 table, evaluated like PrelinEval8 (round 6)
     }
     if constexpr (DEPTH == 16 && PLANES >= 3) {
-        if (p.icc16_clut != nullptr) {              // 16-bit CLUT ICC transform requested
-            constexpr int PXT5 = WriteShape<DST16, PLANES, XS, 5>::PXT;
-            groups = (long long)((p.width + PXT5 - 1) / PXT5) * ((p.nrows + (1 << YS) - 1) >> YS);
-            snprintf(label, kLabelBytes, "write_px<depth=%d,planes=%d,out=%d,dst16=%d,xs=%d,ys=%d,transfer=%d,aligned=%d,icc=5>",
-                     DEPTH, PLANES, OUT, (int)DST16, XS, YS, TRANSFER, (int)aligned);
-            if (aligned) hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, true, 5>), dim3(grid_for(groups, label)), dim3(AG_WPX_BLOCK), 0, st, p);
-            else hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, false, 5>), dim3(grid_for(groups, label)), dim3(AG_WPX_BLOCK), 0, st, p);
-            return hipGetLastError();
-        }
+        if (L.icc == 5) return px(Int<5>());            // the 16-bit CLUT
     }
     if constexpr (DEPTH == 32 && PLANES >= 3) {
-        if (p.icc_p8_stages != nullptr) {           // LUT-based profile: lcms2's float stage program per pixel
-            if constexpr (!kHereIcc8) {             // those kernels live in a code object of their own (AG_WRITE_PART 38)
-                return launch_planes_d32_icc8(p, PLANES, DST16, OUT == kOutRefColor ? AVIFGPU_OUT_REFERENCE : AVIFGPU_OUT_YCBCR, XS, YS, st, label);
-            } else {
-                constexpr int PXT8 = WriteShape<DST16, PLANES, XS, 8>::PXT;
-                groups = (long long)((p.width + PXT8 - 1) / PXT8) * ((p.nrows + (1 << YS) - 1) >> YS);
-                snprintf(label, kLabelBytes, "write_px<depth=%d,planes=%d,out=%d,dst16=%d,xs=%d,ys=%d,transfer=%d,aligned=%d,icc=8>",
-                         DEPTH, PLANES, OUT, (int)DST16, XS, YS, TRANSFER, (int)aligned);
-                const size_t lds = p.icc_p8_lds_words ? (size_t)((p.icc_p8_lds_words + 1) >> 1) * 4 : 0;          // <= 48 KiB
-                if (lds) snprintf(label + strlen(label), kLabelBytes - strlen(label), " lds");
-                if (aligned) hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, true, 8>), dim3(grid_for(groups, label)), dim3(AG_WPX_BLOCK), lds, st, p);
-                else hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, false, 8>), dim3(grid_for(groups, label)), dim3(AG_WPX_BLOCK), lds, st, p);
-                return hipGetLastError();
-            }
+        const int output = OUT == kOutRefColor ? AVIFGPU_OUT_REFERENCE : AVIFGPU_OUT_YCBCR;
+        if (L.icc == 8) {                               // lcms2's float stage program: a code object of its own (AG_WRITE_PART 38)
+            if constexpr (kHereIcc8) return px(Int<8>()); else return launch_planes_d32_icc8(p, PLANES, DST16, output, XS, YS, L, st);
         }
-        if (p.icc_s_tab != nullptr) {               // sampled document curves: table lookup in front of the matrix
-            if constexpr (!kHereIcc6) {             // those kernels live in a code object of their own (AG_WRITE_PART 36)
-                return launch_planes_d32_icc6(p, PLANES, DST16, OUT == kOutRefColor ? AVIFGPU_OUT_REFERENCE : AVIFGPU_OUT_YCBCR, XS, YS, st, label);
-            } else {
-                snprintf(label, kLabelBytes, "write_px<depth=%d,planes=%d,out=%d,dst16=%d,xs=%d,ys=%d,transfer=%d,aligned=%d,icc=6>",
-                         DEPTH, PLANES, OUT, (int)DST16, XS, YS, TRANSFER, (int)aligned);
-                const size_t lds = p.icc_s_lds ? (size_t)(p.icc_s_n[0] + p.icc_s_n[1] + p.icc_s_n[2]) * 4 : 0;      // <= 48 KiB
-                if (lds) snprintf(label + strlen(label), kLabelBytes - strlen(label), " lds");
-                if (aligned) hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, true, 6>), dim3(grid_for(groups, label)), dim3(AG_WPX_BLOCK), lds, st, p);
-                else hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, false, 6>), dim3(grid_for(groups, label)), dim3(AG_WPX_BLOCK), lds, st, p);
-                return hipGetLastError();
-            }
+        if (L.icc == 6) {                               // sampled document curves: a code object of its own (AG_WRITE_PART 36)
+            if constexpr (kHereIcc6) return px(Int<6>()); else return launch_planes_d32_icc6(p, PLANES, DST16, output, XS, YS, L, st);
         }
     }
     if constexpr (!kHerePlain) {
-        return hipErrorInvalidValue;                // parts 36 / 38 hold the icc = 6 / 8 launches only, the streaming part none of write_px
+        return hipErrorInvalidValue;                    // parts 36 / 38 hold the icc = 6 / 8 launches only, the streaming part none of write_px
     } else {
-    if constexpr (DEPTH == 32 && PLANES >= 3) {
-        if (p.icc_trc_type[0] != 0) {               // ICC row transform requested: separate instantiations, the others pay nothing
-            bool linear = true;
-            for (int c = 0; c < 3; ++c) linear = linear && p.icc_trc_linear[c] != 0;
-            if (p.icc_out == 4) {                   // -> sRGB: the SDR (Clip) save of a 32-bit document
-                if constexpr (TRANSFER == 3) {
-                    snprintf(label, kLabelBytes, "write_px<depth=%d,planes=%d,out=%d,dst16=%d,xs=%d,ys=%d,transfer=%d,aligned=%d,icc=4>",
-                             DEPTH, PLANES, OUT, (int)DST16, XS, YS, TRANSFER, (int)aligned);
-                    if (aligned) hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, true, 4>), dim3(grid_icc(groups, label)), dim3(AG_WPX_BLOCK), 0, st, p);
-                    else hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, false, 4>), dim3(grid_icc(groups, label)), dim3(AG_WPX_BLOCK), 0, st, p);
-                    return hipGetLastError();
-                } else {
-                    return hipErrorInvalidValue;    // rejected earlier by fill_write_params
-                }
+        if constexpr (DEPTH == 32 && PLANES >= 3) {     // the parametric stages: separate instantiations, the others pay nothing
+            if (L.icc == 4) {                           // -> sRGB: the SDR (Clip) save of a 32-bit document
+                if constexpr (TRANSFER == 3) return px(Int<4>()); else return hipErrorInvalidValue;
             }
-            snprintf(label, kLabelBytes, "write_px<depth=%d,planes=%d,out=%d,dst16=%d,xs=%d,ys=%d,transfer=%d,aligned=%d,icc=%d>",
-                     DEPTH, PLANES, OUT, (int)DST16, XS, YS, TRANSFER, (int)aligned, linear ? 1 : 2);
-            if (linear) {
-                if (aligned) hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, true, 1>), dim3(grid_px<TRANSFER>(groups, label)), dim3(AG_WPX_BLOCK), 0, st, p);
-                else hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, false, 1>), dim3(grid_px<TRANSFER>(groups, label)), dim3(AG_WPX_BLOCK), 0, st, p);
-            } else {
-                if (aligned) hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, true, 2>), dim3(grid_icc(groups, label)), dim3(AG_WPX_BLOCK), 0, st, p);
-                else hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, false, 2>), dim3(grid_icc(groups, label)), dim3(AG_WPX_BLOCK), 0, st, p);
-            }
-            return hipGetLastError();
+            if (L.icc == 1) return px(Int<1>());
+            if (L.icc == 2) return px(Int<2>());
         }
-    }
-    if (aligned) hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, true>), dim3(grid_px<TRANSFER>(groups, label)), dim3(AG_WPX_BLOCK), 0, st, p);
-    else hipLaunchKernelGGL((write_px<DEPTH, PLANES, OUT, DST16, XS, YS, TRANSFER, false>), dim3(grid_px<TRANSFER>(groups, label)), dim3(AG_WPX_BLOCK), 0, st, p);
-    return hipGetLastError();
+        return px(Int<0>());
     }
 }
 
-#define AG_LAUNCH(DEPTH, PLANES, OUT, DST16, XS, YS, TR) \
-    return launch_one<DEPTH, PLANES, OUT, DST16, XS, YS, TR>(p, st, label)
-
 template <int DEPTH, int PLANES, int OUT, bool DST16, int XS, int YS>
-static hipError_t launch_tr(const WriteParams& p, hipStream_t st, char* label)
+static hipError_t launch_tr(const WriteParams& p, const WriteLaunch& L, hipStream_t st)
 {
-    if constexpr (DEPTH == 32) {
-        switch (p.transfer) {
-        case AVIFGPU_TRANSFER_PQ:       if (pq_hi_launch(p)) AG_LAUNCH(DEPTH, PLANES, OUT, DST16, XS, YS, kTransferPqHi); AG_LAUNCH(DEPTH, PLANES, OUT, DST16, XS, YS, 0);
-        case AVIFGPU_TRANSFER_HLG:      AG_LAUNCH(DEPTH, PLANES, OUT, DST16, XS, YS, 1);
-        case AVIFGPU_TRANSFER_SMPTE428: AG_LAUNCH(DEPTH, PLANES, OUT, DST16, XS, YS, 2);
-        default:                        AG_LAUNCH(DEPTH, PLANES, OUT, DST16, XS, YS, 3);
-        }
-    } else {
-        AG_LAUNCH(DEPTH, PLANES, OUT, DST16, XS, YS, 3);
-    }
+    hipError_t e = hipErrorInvalidValue;
+    if constexpr (DEPTH == 32) with_transfer(L.tr, [&](auto tr) { e = launch_one<DEPTH, PLANES, OUT, DST16, XS, YS, AG_V(tr)>(p, L, st); });
+    else e = launch_one<DEPTH, PLANES, OUT, DST16, XS, YS, AVIFGPU_TRANSFER_CLIP>(p, L, st);
+    return e;
 }
 
 template <int DEPTH, int PLANES, bool DST16>
-static hipError_t launch_out(const WriteParams& p, int output, int xs, int ys, hipStream_t st, char* label)
+static hipError_t launch_out(const WriteParams& p, int output, int xs, int ys, const WriteLaunch& L, hipStream_t st)
 {
     if constexpr (PLANES <= 2) {
-        return launch_tr<DEPTH, PLANES, kOutRefGray, DST16, 0, 0>(p, st, label);
+        return launch_tr<DEPTH, PLANES, kOutRefGray, DST16, 0, 0>(p, L, st);
     } else {
-        if (output == AVIFGPU_OUT_REFERENCE) return launch_tr<DEPTH, PLANES, kOutRefColor, DST16, 0, 0>(p, st, label);
-        if (xs == 0) return launch_tr<DEPTH, PLANES, kOutYcbcr, DST16, 0, 0>(p, st, label);
-        if (ys == 0) return launch_tr<DEPTH, PLANES, kOutYcbcr, DST16, 1, 0>(p, st, label);
-        return launch_tr<DEPTH, PLANES, kOutYcbcr, DST16, 1, 1>(p, st, label);
+        if (output == AVIFGPU_OUT_REFERENCE) return launch_tr<DEPTH, PLANES, kOutRefColor, DST16, 0, 0>(p, L, st);
+        if (xs == 0) return launch_tr<DEPTH, PLANES, kOutYcbcr, DST16, 0, 0>(p, L, st);
+        if (ys == 0) return launch_tr<DEPTH, PLANES, kOutYcbcr, DST16, 1, 0>(p, L, st);
+        return launch_tr<DEPTH, PLANES, kOutYcbcr, DST16, 1, 1>(p, L, st);
     }
 }
 
 template <int DEPTH, int PLANES>
-static hipError_t launch_planes_n(const WriteParams& p, bool dst16, int output, int xs, int ys, hipStream_t st, char* label)
+static hipError_t launch_planes_n(const WriteParams& p, bool dst16, int output, int xs, int ys, const WriteLaunch& L, hipStream_t st)
 {
-    if (dst16) return launch_out<DEPTH, PLANES, true>(p, output, xs, ys, st, label);
+    if (dst16) return launch_out<DEPTH, PLANES, true>(p, output, xs, ys, L, st);
     if constexpr (DEPTH == 32) return hipErrorInvalidValue;          // a 32-bit document is never saved at 8 bit
-    else return launch_out<DEPTH, PLANES, false>(p, output, xs, ys, st, label);
+    else return launch_out<DEPTH, PLANES, false>(p, output, xs, ys, L, st);
 }
 template <int DEPTH>
-static hipError_t launch_planes(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys,
-                                hipStream_t st, char* label)
+static hipError_t launch_planes(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, const WriteLaunch& L, hipStream_t st)
 {
     // 32-bit documents: gray (+ alpha) lives in part 32, RGB(A) -- the fall-back of the streaming kernels -- in part 33 (36: its icc = 6 half)
     constexpr bool gray_here = DEPTH != 32 || AG_WRITE_PART == 0 || AG_WRITE_PART == 32;
     constexpr bool rgb_here = DEPTH != 32 || AG_WRITE_PART == 0 || AG_WRITE_PART == 33 || AG_WRITE_PART == 36 || AG_WRITE_PART == 38;
     switch (planes) {
-    case 1:  if constexpr (gray_here) return launch_planes_n<DEPTH, 1>(p, dst16, output, xs, ys, st, label); else return hipErrorInvalidValue;
-    case 2:  if constexpr (gray_here) return launch_planes_n<DEPTH, 2>(p, dst16, output, xs, ys, st, label); else return hipErrorInvalidValue;
-    case 3:  if constexpr (rgb_here) return launch_planes_n<DEPTH, 3>(p, dst16, output, xs, ys, st, label); else return launch_planes_d32_rgb(p, planes, dst16, output, xs, ys, st, label);
-    default: if constexpr (rgb_here) return launch_planes_n<DEPTH, 4>(p, dst16, output, xs, ys, st, label); else return launch_planes_d32_rgb(p, planes, dst16, output, xs, ys, st, label);
+    case 1:  if constexpr (gray_here) return launch_planes_n<DEPTH, 1>(p, dst16, output, xs, ys, L, st); else return hipErrorInvalidValue;
+    case 2:  if constexpr (gray_here) return launch_planes_n<DEPTH, 2>(p, dst16, output, xs, ys, L, st); else return hipErrorInvalidValue;
+    case 3:  if constexpr (rgb_here) return launch_planes_n<DEPTH, 3>(p, dst16, output, xs, ys, L, st); else return launch_planes_d32_rgb(p, planes, dst16, output, xs, ys, L, st);
+    default: if constexpr (rgb_here) return launch_planes_n<DEPTH, 4>(p, dst16, output, xs, ys, L, st); else return launch_planes_d32_rgb(p, planes, dst16, output, xs, ys, L, st);
     }
 }
 
 // ---- the parts' entry points (see AG_WRITE_PART at the top) ----
 #if AG_WRITE_PART == 0 || AG_WRITE_PART == 8
-hipError_t launch_planes_d8(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, hipStream_t st, char* label)
+hipError_t launch_planes_d8(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, const WriteLaunch& L, hipStream_t st)
 {
-    return launch_planes<8>(p, planes, dst16, output, xs, ys, st, label);
+    return launch_planes<8>(p, planes, dst16, output, xs, ys, L, st);
 }
 #endif
 #if AG_WRITE_PART == 0 || AG_WRITE_PART == 16
-hipError_t launch_planes_d16(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, hipStream_t st, char* label)
+hipError_t launch_planes_d16(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, const WriteLaunch& L, hipStream_t st)
 {
-    return launch_planes<16>(p, planes, dst16, output, xs, ys, st, label);
+    return launch_planes<16>(p, planes, dst16, output, xs, ys, L, st);
 }
 #endif
 #if AG_WRITE_PART == 0 || AG_WRITE_PART == 32
-hipError_t launch_planes_d32(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, hipStream_t st, char* label)
+hipError_t launch_planes_d32(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, const WriteLaunch& L, hipStream_t st)
 {
-    return launch_planes<32>(p, planes, dst16, output, xs, ys, st, label);
+    return launch_planes<32>(p, planes, dst16, output, xs, ys, L, st);
 }
 #endif
 #if AG_WRITE_PART == 0 || AG_WRITE_PART == 33
-hipError_t launch_planes_d32_rgb(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, hipStream_t st, char* label)
+hipError_t launch_planes_d32_rgb(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, const WriteLaunch& L, hipStream_t st)
 {
-    return launch_planes<32>(p, planes, dst16, output, xs, ys, st, label);
+    return launch_planes<32>(p, planes, dst16, output, xs, ys, L, st);
 }
 #endif
-#if AG_WRITE_PART == 0 || AG_WRITE_PART == 36
-hipError_t launch_planes_d32_icc6(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, hipStream_t st, char* label)
+#if AG_WRITE_PART == 36      // (one object: launch_one launches the sampled-curve and the stage-program kernels itself and names neither entry)
+hipError_t launch_planes_d32_icc6(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, const WriteLaunch& L, hipStream_t st)
 {
-#if AG_WRITE_PART == 0
-    (void)p; (void)planes; (void)dst16; (void)output; (void)xs; (void)ys; (void)st; (void)label;
-    return hipErrorInvalidValue;                    // one object: launch_one launches the sampled-curve kernels itself
-#else
-    return launch_planes<32>(p, planes, dst16, output, xs, ys, st, label);     // here launch_one compiles the icc = 6 launches only
-#endif
+    return launch_planes<32>(p, planes, dst16, output, xs, ys, L, st);     // here launch_one compiles the icc = 6 launches only
 }
 #endif
-
-#if AG_WRITE_PART == 0 || AG_WRITE_PART == 38
-hipError_t launch_planes_d32_icc8(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, hipStream_t st, char* label)
+#if AG_WRITE_PART == 38
+hipError_t launch_planes_d32_icc8(const WriteParams& p, int planes, bool dst16, int output, int xs, int ys, const WriteLaunch& L, hipStream_t st)
 {
-#if AG_WRITE_PART == 0
-    (void)p; (void)planes; (void)dst16; (void)output; (void)xs; (void)ys; (void)st; (void)label;
-    return hipErrorInvalidValue;                    // one object: launch_one launches the stage-program kernels itself
-#else
-    return launch_planes<32>(p, planes, dst16, output, xs, ys, st, label);     // here launch_one compiles the icc = 8 launches only
-#endif
+    return launch_planes<32>(p, planes, dst16, output, xs, ys, L, st);     // here launch_one compiles the icc = 8 launches only
 }
 #endif
 
-// AG_IREF8 (round 5): RGBA8 documents through the interleaved hand-off (what integration/ asks for by default; the integer premultiply where the
-// alpha state asks for it) on the streaming hand-off kernel: 0.66 -> 0.73 of 8 TB/s on fresh data.  Round 2 had kept every 8-bit document on
-// the generic kernel on one-set-loop figures (0.75-0.77 there).  The RGB8 hand-off -- a plain copy -- stays generic: 0.76 against 0.71 here.
-#ifndef AG_IREF8
-#define AG_IREF8 1
-#endif
-#ifndef AG_COPY8
-#define AG_COPY8 1
-#endif
-#ifndef AG_RGBA16_TO8
-#define AG_RGBA16_TO8 1
-#endif
-// The streaming launches in three code objects (AG_WRITE_PART 1 / 2 / 3, see the top of the file): every `return` inside one of the two
-// functions below is a launch (or an empty tile) -- *taken says so; falling off the end hands the tile to the next candidate.
-hipError_t launch_stream_int(const WriteParams& p, int depth, int planes, bool dst16, int output, int xs, int ys, int variant, hipStream_t st, char* label, bool* taken);
-hipError_t launch_stream_f32_sub_rgba(const WriteParams& p, int depth, int planes, bool dst16, int output, int xs, int ys, int variant, hipStream_t st, char* label, bool* taken);
+// The streaming launches in three code objects (AG_WRITE_PART 1 / 2 / 3, see the top of the file): the kernels of a decision (WriteKernel,
+// write_dispatch.h, lists them part by part) are launched by the part that holds them.
+hipError_t launch_stream_int(const WriteParams& p, const WriteLaunch& L, int depth, int planes, bool dst16, int xs, int ys, hipStream_t st);
+hipError_t launch_stream_f32_sub_rgba(const WriteParams& p, const WriteLaunch& L, int ys, hipStream_t st);
 #if AG_WRITE_PART == 0 || AG_WRITE_PART == 2
-hipError_t launch_stream_int(const WriteParams& p, int depth, int planes, bool dst16, int output, int xs, int ys, int variant, hipStream_t st, char* label, bool* taken)
+hipError_t launch_stream_int(const WriteParams& p, const WriteLaunch& L, int depth, int planes, bool dst16, int xs, int ys, hipStream_t st)
 {
-    *taken = true;
-    if (depth == 8 && p.icc16_clut != nullptr) { *taken = false; return hipSuccess; }      // an 8-bit document behind a table profile: write_px<..., icc = 7>
-    // 8-bit document, 8-bit hand-off, nothing to premultiply: the reference copies the bytes (round 6)
-    if (AG_COPY8 && (variant & 1) && p.icc8_s1 == nullptr && depth == 8 && !dst16 && p.maxv == 255 && output == AVIFGPU_OUT_REFERENCE &&
-        (planes == 3 || planes == 1 || (planes == 4 && !p.premultiply)) &&
-        (((long long)p.width * planes) & 3) == 0 && ((p.src_row_bytes | p.dst_stride[0]) & 3) == 0 &&
-        ((reinterpret_cast<uintptr_t>(p.src) | reinterpret_cast<uintptr_t>(p.dst[0])) & 3) == 0) {
+    const dim3 grid((int)L.blocks), stream(AG_STREAM_BLOCK);
+    switch (L.kernel) {
+    case kWkCopyRows: {
         CopyParams c = { p.src, p.dst[0], p.src_row_bytes, p.dst_stride[0], (long long)p.width * planes, p.nrows };
-        const bool one = !(variant & 16) && c.nrows > 1 && c.src_stride == c.row_bytes && c.dst_stride == c.row_bytes;     // contiguous on both sides: one row
-        if (one) { c.row_bytes *= c.nrows; c.nrows = 1; }
-        constexpr int kCopyK = AG_COPY_K, kCopyWaves = AG_COPY_BLOCK / 64;
-        const long long waves = ((c.row_bytes + 1024 * kCopyK - 1) / (1024 * kCopyK)) * c.nrows;
-        if (waves == 0) return hipSuccess;
-        if (waves + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            const long long need = (waves + kCopyWaves - 1) / kCopyWaves;
-            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / kCopyWaves, variant);
-            snprintf(label, kLabelBytes, "write_copy_rows_stream<planes=%d>", planes);
-            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / kCopyWaves);
-            if (one) snprintf(label + strlen(label), kLabelBytes - strlen(label), " flat");
-            hipLaunchKernelGGL((write_copy_rows_stream<kCopyK>), dim3((int)blocks), dim3(AG_COPY_BLOCK), 0, st, c);
-            return hipGetLastError();
-        }
+        if (L.one) { c.row_bytes *= c.nrows; c.nrows = 1; }       // contiguous on both sides: one row
+        hipLaunchKernelGGL((write_copy_rows_stream<AG_COPY_K>), grid, dim3(AG_COPY_BLOCK), 0, st, c);
+        break;
     }
-    if ((variant & 1) && p.icc16_clut == nullptr && p.icc8_s1 == nullptr && (depth == 16 || (AG_IREF8 && depth == 8 && planes == 4)) &&
-        ((planes >= 3 && output == AVIFGPU_OUT_REFERENCE) || (planes == 1 && depth == 16)) &&      // (Gray16 -> Y plane: elementwise too, round 5)
-        ((long long)p.width * planes * (depth / 8)) % 16 == 0 && (p.src_row_bytes & 15) == 0 && (reinterpret_cast<uintptr_t>(p.src) & 15) == 0 &&
-        ((reinterpret_cast<uintptr_t>(p.dst[0]) | (uintptr_t)p.dst_stride[0]) & 15) == 0) {
-        const long long nv = (long long)p.width * planes * (depth / 8) / 16;
-        const long long waves = ((nv + 255) / 256) * p.nrows;
-        if (waves == 0) return hipSuccess;
-        if (waves + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            const long long need = (waves + kStreamWaves - 1) / kStreamWaves;
-            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / kStreamWaves, variant);
-            snprintf(label, kLabelBytes, "write_int_ref_stream<depth=%d,planes=%d,dst16=%d>", depth, planes, (int)dst16);
-            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / kStreamWaves);
-#define AG_IREF(D, P) do { if (dst16) hipLaunchKernelGGL((write_int_ref_stream<D, P, true>), dim3((int)blocks), dim3(AG_STREAM_BLOCK), 0, st, p); \
-                           else hipLaunchKernelGGL((write_int_ref_stream<D, P, false>), dim3((int)blocks), dim3(AG_STREAM_BLOCK), 0, st, p); } while (0)
-            if (depth == 8) AG_IREF(8, 4);
-            else { if (planes == 4) AG_IREF(16, 4); else if (planes == 1) AG_IREF(16, 1); else AG_IREF(16, 3); }
-#undef AG_IREF
-            return hipGetLastError();
-        }
+    case kWkIntRef:
+        with_bool(dst16, [&](auto d16) {
+            if (depth == 8) hipLaunchKernelGGL((write_int_ref_stream<8, 4, AG_V(d16)>), grid, stream, 0, st, p);
+            else if (planes == 4) hipLaunchKernelGGL((write_int_ref_stream<16, 4, AG_V(d16)>), grid, stream, 0, st, p);
+            else if (planes == 1) hipLaunchKernelGGL((write_int_ref_stream<16, 1, AG_V(d16)>), grid, stream, 0, st, p);
+            else hipLaunchKernelGGL((write_int_ref_stream<16, 3, AG_V(d16)>), grid, stream, 0, st, p);
+        });
+        break;
+    case kWkGa16: hipLaunchKernelGGL((write_ga_stream<16, AVIFGPU_TRANSFER_CLIP>), grid, dim3(AG_GA_BLOCK), 0, st, p); break;
+    case kWkRgb8:
+        with_chroma(xs, ys, p.nearest, [&](auto x, auto y, auto nr) {
+            constexpr int wpb = AG_V(y) ? 2 : 4;
+            hipLaunchKernelGGL((write_rgb8_ycbcr_hot<AG_V(x), AG_V(y), AG_V(nr), wpb>), grid, dim3(64 * wpb), 0, st, p);
+        });
+        break;
+    case kWkRgb8To16:
+        with_chroma(xs, ys, p.nearest, [&](auto x, auto y, auto nr) {
+            hipLaunchKernelGGL((write_rgb8_ycbcr16_hot<AG_V(x), AG_V(y), AG_V(nr), AG_RGB8_16_WAVES>), grid, dim3(64 * AG_RGB8_16_WAVES), 0, st, p);
+        });
+        break;
+    case kWkRgba8:
+        with_chroma(xs, ys, p.nearest, [&](auto x, auto y, auto nr) {
+            with_bool(p.premultiply, [&](auto pm) { hipLaunchKernelGGL((write_rgba8_ycbcra_hot<AG_V(x), AG_V(y), AG_V(nr), AG_V(pm)>), grid, dim3(256), 0, st, p); });
+        });
+        break;
+    case kWkRgb16:
+        with_bool(!dst16, [&](auto to8) { hipLaunchKernelGGL((write_rgb16_ycbcr444_hot<AG_RGB16_NS, AG_V(to8)>), grid, stream, 0, st, p); });
+        break;
+    case kWkRgba16:
+        with_bool(!dst16, [&](auto to8) { hipLaunchKernelGGL((write_rgba16_ycbcra444_hot<AG_V(to8)>), grid, stream, 0, st, p); });
+        break;
+    case kWkRgba16Sub:
+        with_bool(ys, [&](auto y) { with_bool(p.nearest, [&](auto nr) { with_bool(!dst16, [&](auto to8) {
+            hipLaunchKernelGGL((write_rgba16_ycbcra_sub_hot<AG_V(y), AG_V(nr), AG_V(to8)>), grid, stream, 0, st, p); }); }); });
+        break;
+    case kWkRgb16Sub:                               // (u16 planes outermost: kernels are emitted in the order they are instantiated in, and tools/compare_isa.py sees the padding behind the last)
+        with_bool(dst16, [&](auto d16) { with_bool(ys, [&](auto y) {
+            hipLaunchKernelGGL((write_rgb16_ycbcr_sub_hot<AG_V(y), !AG_V(d16)>), grid, stream, 0, st, p); }); });
+        break;
+    default: return hipErrorInvalidValue;
     }
-    // Gray16 + alpha -> Y and Alpha u16 planes (round 5): widths of whole 4-pixel vectors, dword-aligned rows and planes
-    if (depth == 16 && (p.width % 4) == 0 && (variant & 1) && planes == 2 && dst16 && p.dst[3] != nullptr && (p.src_row_bytes & 3) == 0 && (reinterpret_cast<uintptr_t>(p.src) & 3) == 0 &&
-        ((reinterpret_cast<uintptr_t>(p.dst[0]) | reinterpret_cast<uintptr_t>(p.dst[3]) | (uintptr_t)p.dst_stride[0] | (uintptr_t)p.dst_stride[3]) & 3) == 0) {
-        const long long waves = (((long long)p.width / 4 + 255) / 256) * p.nrows;
-        if (waves == 0) return hipSuccess;
-        if (waves + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            const long long need = (waves + kGaWaves - 1) / kGaWaves;
-            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / kGaWaves, variant);
-            snprintf(label, kLabelBytes, "write_ga_stream<depth=16>");
-            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / kGaWaves);
-            hipLaunchKernelGGL((write_ga_stream<16, AVIFGPU_TRANSFER_CLIP>), dim3((int)blocks), dim3(AG_GA_BLOCK), 0, st, p);
-            return hipGetLastError();
-        }
-    }
-    // RGB8 -> u8 Y, Cb, Cr (the plug-in's default save; BASELINE C2): widths of whole 8-pixel groups, dword-aligned rows and planes
-    if (AG_RGB8_HOT && (variant & 1) && p.icc8_s1 == nullptr && depth == 8 && planes == 3 && !dst16 && output == AVIFGPU_OUT_YCBCR && p.maxv == 255 &&
-        (p.width % 8) == 0 && (p.src_row_bytes & 3) == 0 && (reinterpret_cast<uintptr_t>(p.src) & 3) == 0 &&
-        ((reinterpret_cast<uintptr_t>(p.dst[0]) | reinterpret_cast<uintptr_t>(p.dst[1]) | reinterpret_cast<uintptr_t>(p.dst[2]) |
-          (uintptr_t)p.dst_stride[0] | (uintptr_t)p.dst_stride[1] | (uintptr_t)p.dst_stride[2]) & 3) == 0) {
-        const long long spans = (long long)((p.width + 1023) / 1024) * ((p.nrows + (1 << ys) - 1) >> ys);
-        if (spans == 0) return hipSuccess;
-        if (spans + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            const int wpb = ys ? 2 : 4;                                            // waves per workgroup
-            const long long need = (spans + wpb - 1) / wpb;
-            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / wpb, variant);
-            snprintf(label, kLabelBytes, "write_rgb8_ycbcr_hot<xs=%d,ys=%d,nearest=%d>", xs, ys, (xs || ys) ? p.nearest : 0);
-            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / wpb);
-#define AG_R8(XS_, YS_, NR_) hipLaunchKernelGGL((write_rgb8_ycbcr_hot<XS_, YS_, NR_, (YS_ ? 2 : 4)>), dim3((int)blocks), dim3(64 * (YS_ ? 2 : 4)), 0, st, p)
-            if (xs == 0) AG_R8(0, 0, false);
-            else if (ys == 0) { if (p.nearest) AG_R8(1, 0, true); else AG_R8(1, 0, false); }
-            else { if (p.nearest) AG_R8(1, 1, true); else AG_R8(1, 1, false); }
-#undef AG_R8
-            return hipGetLastError();
-        }
-    }
-    // RGB8 -> u16 Y, Cb, Cr (round 6): an 8-bit document saved at 10 / 12 bit; the same conditions
-    if (AG_RGB8_HOT && (variant & 1) && p.icc8_s1 == nullptr && depth == 8 && planes == 3 && dst16 && output == AVIFGPU_OUT_YCBCR && (p.maxv == 1023 || p.maxv == 4095) &&
-        (p.width % 8) == 0 && (p.src_row_bytes & 3) == 0 && (reinterpret_cast<uintptr_t>(p.src) & 3) == 0 &&
-        ((reinterpret_cast<uintptr_t>(p.dst[0]) | reinterpret_cast<uintptr_t>(p.dst[1]) | reinterpret_cast<uintptr_t>(p.dst[2]) |
-          (uintptr_t)p.dst_stride[0] | (uintptr_t)p.dst_stride[1] | (uintptr_t)p.dst_stride[2]) & 3) == 0) {
-        const long long spans = (long long)((p.width + 1023) / 1024) * ((p.nrows + (1 << ys) - 1) >> ys);
-        if (spans == 0) return hipSuccess;
-        if (spans + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            constexpr int wpb = AG_RGB8_16_WAVES;
-            const long long need = (spans + wpb - 1) / wpb;
-            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / wpb, variant);
-            snprintf(label, kLabelBytes, "write_rgb8_ycbcr16_hot<xs=%d,ys=%d,nearest=%d>", xs, ys, (xs || ys) ? p.nearest : 0);
-            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / wpb);
-#define AG_R816(XS_, YS_, NR_) hipLaunchKernelGGL((write_rgb8_ycbcr16_hot<XS_, YS_, NR_, wpb>), dim3((int)blocks), dim3(64 * wpb), 0, st, p)
-            if (xs == 0) AG_R816(0, 0, false);
-            else if (ys == 0) { if (p.nearest) AG_R816(1, 0, true); else AG_R816(1, 0, false); }
-            else { if (p.nearest) AG_R816(1, 1, true); else AG_R816(1, 1, false); }
-#undef AG_R816
-            return hipGetLastError();
-        }
-    }
-    // RGBA8 -> u8 Y, Cb, Cr, A (a transparent 8-bit document's save): widths of whole 8-pixel groups, dword-aligned rows and planes
-    if (AG_RGB8_HOT && (variant & 1) && p.icc8_s1 == nullptr && depth == 8 && planes == 4 && !dst16 && output == AVIFGPU_OUT_YCBCR && p.maxv == 255 && p.dst[3] != nullptr &&
-        (p.width % 8) == 0 && (p.src_row_bytes & 3) == 0 && (reinterpret_cast<uintptr_t>(p.src) & 3) == 0 &&
-        ((reinterpret_cast<uintptr_t>(p.dst[0]) | reinterpret_cast<uintptr_t>(p.dst[1]) | reinterpret_cast<uintptr_t>(p.dst[2]) | reinterpret_cast<uintptr_t>(p.dst[3]) |
-          (uintptr_t)p.dst_stride[0] | (uintptr_t)p.dst_stride[1] | (uintptr_t)p.dst_stride[2] | (uintptr_t)p.dst_stride[3]) & 3) == 0) {
-        const long long spans = (long long)((p.width + 511) / 512) * ((p.nrows + (1 << ys) - 1) >> ys);
-        if (spans == 0) return hipSuccess;
-        if (spans + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            const long long need = (spans + 3) / 4;
-            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP, variant);
-            snprintf(label, kLabelBytes, "write_rgba8_ycbcra_hot<xs=%d,ys=%d,nearest=%d,premultiply=%d>", xs, ys, (xs || ys) ? p.nearest : 0, p.premultiply);
-            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP);
-#define AG_RA8(XS_, YS_, NR_) do { if (p.premultiply) hipLaunchKernelGGL((write_rgba8_ycbcra_hot<XS_, YS_, NR_, true>), dim3((int)blocks), dim3(256), 0, st, p); \
-                                   else hipLaunchKernelGGL((write_rgba8_ycbcra_hot<XS_, YS_, NR_, false>), dim3((int)blocks), dim3(256), 0, st, p); } while (0)
-            if (xs == 0) AG_RA8(0, 0, false);
-            else if (ys == 0) { if (p.nearest) AG_RA8(1, 0, true); else AG_RA8(1, 0, false); }
-            else { if (p.nearest) AG_RA8(1, 1, true); else AG_RA8(1, 1, false); }
-#undef AG_RA8
-            return hipGetLastError();
-        }
-    }
-    // RGB16 -> u16 Y, Cb, Cr 4:4:4 (BASELINE C3).  At every size since round 5: round 2 had gated it to launches of >= 40 Mpx because the
-    // generic kernel "held 0.76-0.80 up to ~45 Mpx" -- in a one-set loop, where its allocating loads re-read the Infinity Cache.  On fresh
-    // data the streaming kernel wins wherever it was gated off: 6000 x 4000 0.68 -> 0.74 of 8 TB/s, 4096^2 0.64 -> 0.70
-    // (profiles/r05/rgb16_streaming_gates_fresh_data.txt).  Both produce the same bytes (tests/test_gpu_kernel_equivalence.py).
-#ifndef AG_RGB16_MIN_PX
-#define AG_RGB16_MIN_PX 0
-#endif
-    if ((variant & 1) && p.icc16_clut == nullptr && depth == 16 && planes == 3 && (dst16 || p.maxv == 255) && output == AVIFGPU_OUT_YCBCR && xs == 0 && ys == 0 &&
-        ((long long)p.width * p.nrows >= AG_RGB16_MIN_PX || (variant & 8)) &&
-        (p.width % 8) == 0 && (p.src_row_bytes & 15) == 0 && (reinterpret_cast<uintptr_t>(p.src) & 15) == 0 &&
-        ((reinterpret_cast<uintptr_t>(p.dst[0]) | reinterpret_cast<uintptr_t>(p.dst[1]) | reinterpret_cast<uintptr_t>(p.dst[2]) |
-          (uintptr_t)p.dst_stride[0] | (uintptr_t)p.dst_stride[1] | (uintptr_t)p.dst_stride[2]) & 15) == 0) {
-        const long long spans = (long long)((p.width + 511) / 512) * p.nrows;
-        if (spans == 0) return hipSuccess;
-        if (spans + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            const long long need = (spans + kStreamWaves * AG_RGB16_NS - 1) / (kStreamWaves * AG_RGB16_NS);
-            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / kStreamWaves, variant);
-            snprintf(label, kLabelBytes, "write_rgb16_ycbcr444_hot<ns=%d%s>", AG_RGB16_NS, dst16 ? "" : ",to8");
-            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / kStreamWaves);
-            if (dst16) hipLaunchKernelGGL((write_rgb16_ycbcr444_hot<AG_RGB16_NS>), dim3((int)blocks), dim3(AG_STREAM_BLOCK), 0, st, p);
-            else hipLaunchKernelGGL((write_rgb16_ycbcr444_hot<AG_RGB16_NS, true>), dim3((int)blocks), dim3(AG_STREAM_BLOCK), 0, st, p);
-            return hipGetLastError();
-        }
-    }
-#ifndef AG_RGBA16_MIN_PX
-#define AG_RGBA16_MIN_PX 0
-#endif
-    // RGBA16 -> u16 Y, Cb, Cr, A 4:4:4
-    if ((variant & 1) && p.icc16_clut == nullptr && depth == 16 && planes == 4 && (dst16 || (AG_RGBA16_TO8 && p.maxv == 255)) && output == AVIFGPU_OUT_YCBCR && xs == 0 && ys == 0 &&
-        ((long long)p.width * p.nrows >= AG_RGBA16_MIN_PX || (variant & 8)) && p.dst[3] != nullptr &&
-        (p.width % 8) == 0 && (p.src_row_bytes & 15) == 0 && (reinterpret_cast<uintptr_t>(p.src) & 15) == 0 &&
-        ((reinterpret_cast<uintptr_t>(p.dst[0]) | reinterpret_cast<uintptr_t>(p.dst[1]) | reinterpret_cast<uintptr_t>(p.dst[2]) | reinterpret_cast<uintptr_t>(p.dst[3]) |
-          (uintptr_t)p.dst_stride[0] | (uintptr_t)p.dst_stride[1] | (uintptr_t)p.dst_stride[2] | (uintptr_t)p.dst_stride[3]) & 15) == 0) {
-        const long long spans = (long long)((p.width + 511) / 512) * p.nrows;
-        if (spans == 0) return hipSuccess;
-        if (spans + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            const long long need = (spans + kStreamWaves - 1) / kStreamWaves;
-            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / kStreamWaves, variant);
-            snprintf(label, kLabelBytes, "write_rgba16_ycbcra444_hot%s", dst16 ? "" : "<to8>");
-            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / kStreamWaves);
-            if (dst16) hipLaunchKernelGGL((write_rgba16_ycbcra444_hot<false>), dim3((int)blocks), dim3(AG_STREAM_BLOCK), 0, st, p);
-            else hipLaunchKernelGGL((write_rgba16_ycbcra444_hot<true>), dim3((int)blocks), dim3(AG_STREAM_BLOCK), 0, st, p);
-            return hipGetLastError();
-        }
-    }
-    // RGBA16 -> u16 Y, Cb, Cr (4:2:2 / 4:2:0), A: the plug-in's default save of a transparent 16-bit document (round 5, last series)
-    if ((variant & 1) && p.icc16_clut == nullptr && depth == 16 && planes == 4 && (dst16 || (AG_RGBA16_TO8 && p.maxv == 255)) && output == AVIFGPU_OUT_YCBCR && xs == 1 && p.dst[3] != nullptr &&
-        (p.width % 8) == 0 && (p.src_row_bytes & 15) == 0 && (reinterpret_cast<uintptr_t>(p.src) & 15) == 0 &&
-        ((reinterpret_cast<uintptr_t>(p.dst[0]) | reinterpret_cast<uintptr_t>(p.dst[3]) | (uintptr_t)p.dst_stride[0] | (uintptr_t)p.dst_stride[3]) & 15) == 0 &&
-        ((reinterpret_cast<uintptr_t>(p.dst[1]) | reinterpret_cast<uintptr_t>(p.dst[2]) | (uintptr_t)p.dst_stride[1] | (uintptr_t)p.dst_stride[2]) & 7) == 0) {
-        const long long spans = (long long)((p.width + 511) / 512) * ((p.nrows + (1 << ys) - 1) >> ys);
-        if (spans == 0) return hipSuccess;
-        if (spans + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            const long long need = (spans + kStreamWaves - 1) / kStreamWaves;
-            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / kStreamWaves, variant);
-            snprintf(label, kLabelBytes, "write_rgba16_ycbcra_sub_hot<ys=%d,nearest=%d%s>", ys, p.nearest, dst16 ? "" : ",to8");
-            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / kStreamWaves);
-#define AG_RA16B(YS_, T8) do { if (p.nearest) hipLaunchKernelGGL((write_rgba16_ycbcra_sub_hot<YS_, true, T8>), dim3((int)blocks), dim3(AG_STREAM_BLOCK), 0, st, p); \
-                               else hipLaunchKernelGGL((write_rgba16_ycbcra_sub_hot<YS_, false, T8>), dim3((int)blocks), dim3(AG_STREAM_BLOCK), 0, st, p); } while (0)
-#define AG_RA16(YS_) do { if (dst16) AG_RA16B(YS_, false); else AG_RA16B(YS_, true); } while (0)
-            if (ys) AG_RA16(1); else AG_RA16(0);
-#undef AG_RA16
-#undef AG_RA16B
-            return hipGetLastError();
-        }
-    }
-    // RGB16 -> u16 Y, Cb, Cr 4:2:2 / 4:2:0.  Any width of whole 8-pixel groups since round 5: round 2 kept rows with a ragged last span
-    // (6000, 7952 wide) on the generic kernel, "4-6 % faster" there in a one-set loop; on fresh data the streaming kernel is 4-6 % ahead
-    // on exactly those rows (7952 x 5304 4:2:0 0.64 -> 0.67, 4:2:2 0.72 -> 0.765, 6000 x 4000 4:2:0 0.61 -> 0.65).  Same bytes either way.
-    if ((variant & 1) && p.icc16_clut == nullptr && depth == 16 && planes == 3 && (dst16 || p.maxv == 255) && output == AVIFGPU_OUT_YCBCR && xs == 1 &&
-        (p.width % 8) == 0 && (p.src_row_bytes & 15) == 0 && (reinterpret_cast<uintptr_t>(p.src) & 15) == 0 &&
-        ((reinterpret_cast<uintptr_t>(p.dst[0]) | reinterpret_cast<uintptr_t>(p.dst[1]) | reinterpret_cast<uintptr_t>(p.dst[2]) |
-          (uintptr_t)p.dst_stride[0] | (uintptr_t)p.dst_stride[1] | (uintptr_t)p.dst_stride[2]) & 15) == 0) {
-        const long long spans = (long long)((p.width + 511) / 512) * ((p.nrows + (1 << ys) - 1) >> ys);
-        if (spans == 0) return hipSuccess;
-        if (spans + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            const long long need = (spans + kStreamWaves - 1) / kStreamWaves;
-            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / kStreamWaves, variant);
-            snprintf(label, kLabelBytes, "write_rgb16_ycbcr_sub_hot<ys=%d%s>", ys, dst16 ? "" : ",to8");
-            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / kStreamWaves);
-            if (dst16) { if (ys) hipLaunchKernelGGL((write_rgb16_ycbcr_sub_hot<1>), dim3((int)blocks), dim3(AG_STREAM_BLOCK), 0, st, p);
-                         else hipLaunchKernelGGL((write_rgb16_ycbcr_sub_hot<0>), dim3((int)blocks), dim3(AG_STREAM_BLOCK), 0, st, p); }
-            else { if (ys) hipLaunchKernelGGL((write_rgb16_ycbcr_sub_hot<1, true>), dim3((int)blocks), dim3(AG_STREAM_BLOCK), 0, st, p);
-                   else hipLaunchKernelGGL((write_rgb16_ycbcr_sub_hot<0, true>), dim3((int)blocks), dim3(AG_STREAM_BLOCK), 0, st, p); }
-            return hipGetLastError();
-        }
-    }
-    *taken = false;
-    return hipSuccess;
+    return hipGetLastError();
 }
 #endif
 #if AG_WRITE_PART == 0 || AG_WRITE_PART == 3
-hipError_t launch_stream_f32_sub_rgba(const WriteParams& p, int depth, int planes, bool dst16, int output, int xs, int ys, int variant, hipStream_t st, char* label, bool* taken)
+hipError_t launch_stream_f32_sub_rgba(const WriteParams& p, const WriteLaunch& L, int ys, hipStream_t st)
 {
-    *taken = true;
-    // Gray32 + alpha -> Y and Alpha u16 planes (round 5): even widths, dword-aligned rows and planes
-    if (depth == 32 && (p.width % 2) == 0 && (variant & 1) && planes == 2 && dst16 && p.dst[3] != nullptr && (p.src_row_bytes & 3) == 0 && (reinterpret_cast<uintptr_t>(p.src) & 3) == 0 &&
-        ((reinterpret_cast<uintptr_t>(p.dst[0]) | reinterpret_cast<uintptr_t>(p.dst[3]) | (uintptr_t)p.dst_stride[0] | (uintptr_t)p.dst_stride[3]) & 3) == 0) {
-        const long long waves = (((long long)p.width / 2 + 255) / 256) * p.nrows;
-        if (waves == 0) return hipSuccess;
-        if (waves + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            const long long need = (waves + kGaWaves - 1) / kGaWaves;
-            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / kGaWaves, variant);
-            snprintf(label, kLabelBytes, "write_ga_stream<depth=32,transfer=%d>", p.transfer);
-            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / kGaWaves);
-            if (p.transfer == AVIFGPU_TRANSFER_PQ) {
-                if (pq_hi_launch(p)) hipLaunchKernelGGL((write_ga_stream<32, kTransferPqHi>), dim3((int)blocks), dim3(AG_GA_BLOCK), 0, st, p);
-                else hipLaunchKernelGGL((write_ga_stream<32, AVIFGPU_TRANSFER_PQ>), dim3((int)blocks), dim3(AG_GA_BLOCK), 0, st, p);
-            } else {
-                hipLaunchKernelGGL((write_ga_stream<32, AVIFGPU_TRANSFER_CLIP>), dim3((int)blocks), dim3(AG_GA_BLOCK), 0, st, p);   // (gray saves: PQ or Clip, avifgpu_api.hip)
-            }
-            return hipGetLastError();
-        }
+    const dim3 grid((int)L.blocks), rgba(AG_RGBA_STREAM_BLOCK), f32(AG_F32_STREAM_BLOCK);
+    switch (L.kernel) {
+    case kWkGa32:                                   // (gray saves: PQ or Clip, avifgpu_api.hip)
+        if (L.tr == kTransferPqHi) hipLaunchKernelGGL((write_ga_stream<32, kTransferPqHi>), grid, dim3(AG_GA_BLOCK), 0, st, p);
+        else if (L.tr == AVIFGPU_TRANSFER_PQ) hipLaunchKernelGGL((write_ga_stream<32, AVIFGPU_TRANSFER_PQ>), grid, dim3(AG_GA_BLOCK), 0, st, p);
+        else hipLaunchKernelGGL((write_ga_stream<32, AVIFGPU_TRANSFER_CLIP>), grid, dim3(AG_GA_BLOCK), 0, st, p);
+        break;
+    case kWkRgba32Sub:
+        with_transfer(L.tr, [&](auto tr) { with_bool(ys, [&](auto y) { with_bool(p.nearest, [&](auto nr) {
+            hipLaunchKernelGGL((write_rgba32_ycbcra_sub_hot<AG_V(tr), AG_V(y), AG_V(nr)>), grid, rgba, 0, st, p); }); }); });
+        break;
+    case kWkRgba32:                                 // the sRGB output curve (4) goes with Clip alone
+        if (L.icc == 4) hipLaunchKernelGGL((write_rgba32_ycbcra444_hot<AVIFGPU_TRANSFER_CLIP, 4>), grid, rgba, 0, st, p);
+        else with_transfer(L.tr, [&](auto tr) {
+            if (L.icc == 1) hipLaunchKernelGGL((write_rgba32_ycbcra444_hot<AG_V(tr), 1>), grid, rgba, 0, st, p);
+            else if (L.icc == 2) hipLaunchKernelGGL((write_rgba32_ycbcra444_hot<AG_V(tr), 2>), grid, rgba, 0, st, p);
+            else hipLaunchKernelGGL((write_rgba32_ycbcra444_hot<AG_V(tr), 0>), grid, rgba, 0, st, p);
+        });
+        break;
+    case kWkRgb32Sub:
+        with_bool(ys, [&](auto y) { with_bool(p.nearest, [&](auto nr) {
+            if (L.icc == 4) hipLaunchKernelGGL((write_rgb32_ycbcr_sub_hot<AVIFGPU_TRANSFER_CLIP, 1, AG_V(y), 4, AG_V(nr)>), grid, f32, 0, st, p);
+            else with_transfer(L.tr, [&](auto tr) {
+                if (L.icc == 1) hipLaunchKernelGGL((write_rgb32_ycbcr_sub_hot<AG_V(tr), 1, AG_V(y), 1, AG_V(nr)>), grid, f32, 0, st, p);
+                else if (L.icc == 2) hipLaunchKernelGGL((write_rgb32_ycbcr_sub_hot<AG_V(tr), 1, AG_V(y), 2, AG_V(nr)>), grid, f32, 0, st, p);
+                else hipLaunchKernelGGL((write_rgb32_ycbcr_sub_hot<AG_V(tr), 1, AG_V(y), 0, AG_V(nr)>), grid, f32, 0, st, p);
+            });
+        }); });
+        break;
+    default: return hipErrorInvalidValue;
     }
-// RGBA f32 -> Y, Cb, Cr (4:2:2 / 4:2:0), A: the plug-in's default save of a transparent 32-bit document (no ICC variant: those stay generic)
-    if ((variant & 1) && p.icc_trc_type[0] == 0 && p.icc_s_tab == nullptr && depth == 32 && planes == 4 && dst16 && output == AVIFGPU_OUT_YCBCR && xs == 1 &&
-        (p.src_row_bytes & 3) == 0 && (reinterpret_cast<uintptr_t>(p.src) & 3) == 0 && p.dst[3] != nullptr &&
-        ((reinterpret_cast<uintptr_t>(p.dst[0]) | reinterpret_cast<uintptr_t>(p.dst[1]) | reinterpret_cast<uintptr_t>(p.dst[2]) |
-          reinterpret_cast<uintptr_t>(p.dst[3]) | (uintptr_t)p.dst_stride[0] | (uintptr_t)p.dst_stride[1] | (uintptr_t)p.dst_stride[2] |
-          (uintptr_t)p.dst_stride[3]) & 3) == 0) {
-        const long long spans = (long long)((p.width + 255) / 256) * ((p.nrows + (1 << ys) - 1) >> ys);
-        if (spans == 0) return hipSuccess;
-        if (spans + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            const long long need = (spans + kRgbaWaves - 1) / kRgbaWaves;
-            const long long blocks = capped_blocks(need, AG_RGBA_BLOCK_CAP * 4 / kRgbaWaves, variant);
-            snprintf(label, kLabelBytes, "write_rgba32_ycbcra_sub_hot<transfer=%d,xs=1,ys=%d,nearest=%d>", p.transfer, ys, p.nearest);
-            label_cap(label, blocks, need, AG_RGBA_BLOCK_CAP * 4 / kRgbaWaves);
-#define AG_RSUB3(TR, YS_, NR_) hipLaunchKernelGGL((write_rgba32_ycbcra_sub_hot<TR, YS_, NR_>), dim3((int)blocks), dim3(AG_RGBA_STREAM_BLOCK), 0, st, p)
-#define AG_RSUB2(TR, YS_) do { if (p.nearest) AG_RSUB3(TR, YS_, true); else AG_RSUB3(TR, YS_, false); } while (0)
-#define AG_RSUB(TR) do { if (ys) AG_RSUB2(TR, 1); else AG_RSUB2(TR, 0); } while (0)
-            switch (p.transfer) {
-            case AVIFGPU_TRANSFER_PQ:       if (pq_hi_launch(p)) AG_RSUB(kTransferPqHi); else AG_RSUB(AVIFGPU_TRANSFER_PQ); break;
-            case AVIFGPU_TRANSFER_HLG:      AG_RSUB(AVIFGPU_TRANSFER_HLG); break;
-            case AVIFGPU_TRANSFER_SMPTE428: AG_RSUB(AVIFGPU_TRANSFER_SMPTE428); break;
-            default:                        AG_RSUB(AVIFGPU_TRANSFER_CLIP); break;
-            }
-#undef AG_RSUB
-#undef AG_RSUB2
-#undef AG_RSUB3
-            return hipGetLastError();
-        }
-    }
-#ifndef AG_RGBA_HOT_ENABLE
-#define AG_RGBA_HOT_ENABLE 1
-#endif
-    const bool rgba_lin = AG_ICC1_HOT && p.icc_trc_type[0] != 0 && p.icc_trc_linear[0] && p.icc_trc_linear[1] && p.icc_trc_linear[2];
-    const bool rgba_icc1 = rgba_lin && p.icc_out == 0;
-    const bool rgba_icc4 = rgba_lin && p.icc_out == 4 && p.transfer == AVIFGPU_TRANSFER_CLIP && AG_ICC_FASTPOW;
-    const bool rgba_icc2 = AG_ICC2_HOT && p.icc_trc_type[0] != 0 && p.icc_same_simple && p.icc_out == 0;
-    if (AG_RGBA_HOT_ENABLE && (variant & 1) && (p.icc_trc_type[0] == 0 || rgba_icc1 || rgba_icc4 || rgba_icc2) && depth == 32 && planes == 4 && dst16 && output == AVIFGPU_OUT_YCBCR && xs == 0 && ys == 0 &&
-        (p.src_row_bytes & 15) == 0 && (reinterpret_cast<uintptr_t>(p.src) & 15) == 0 && p.dst[3] != nullptr &&
-        ((reinterpret_cast<uintptr_t>(p.dst[0]) | reinterpret_cast<uintptr_t>(p.dst[1]) | reinterpret_cast<uintptr_t>(p.dst[2]) |
-          reinterpret_cast<uintptr_t>(p.dst[3]) | (uintptr_t)p.dst_stride[0] | (uintptr_t)p.dst_stride[1] | (uintptr_t)p.dst_stride[2] |
-          (uintptr_t)p.dst_stride[3]) & 15) == 0) {
-        const long long spans = (long long)((p.width + 64 * AG_RGBA_HOT_PXL - 1) / (64 * AG_RGBA_HOT_PXL)) * p.nrows;
-        if (spans == 0) return hipSuccess;
-        if (spans + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            const long long need = (spans + kRgbaWaves - 1) / kRgbaWaves;
-            const long long blocks = capped_blocks(need, AG_RGBA_BLOCK_CAP * 4 / kRgbaWaves, variant);
-            snprintf(label, kLabelBytes, "write_rgba32_ycbcra444_hot<transfer=%d>%s", p.transfer, rgba_icc1 ? " icc=1" : rgba_icc4 ? " icc=4" : rgba_icc2 ? " icc=2" : "");
-            label_cap(label, blocks, need, AG_RGBA_BLOCK_CAP * 4 / kRgbaWaves);
-            if (rgba_icc4) { hipLaunchKernelGGL((write_rgba32_ycbcra444_hot<AVIFGPU_TRANSFER_CLIP, 4>), dim3((int)blocks), dim3(AG_RGBA_STREAM_BLOCK), 0, st, p); return hipGetLastError(); }
-#define AG_RGBA(TR) do { if (rgba_icc1) hipLaunchKernelGGL((write_rgba32_ycbcra444_hot<TR, 1>), dim3((int)blocks), dim3(AG_RGBA_STREAM_BLOCK), 0, st, p); \
-                         else if (rgba_icc2) hipLaunchKernelGGL((write_rgba32_ycbcra444_hot<TR, 2>), dim3((int)blocks), dim3(AG_RGBA_STREAM_BLOCK), 0, st, p); \
-                         else hipLaunchKernelGGL((write_rgba32_ycbcra444_hot<TR, 0>), dim3((int)blocks), dim3(AG_RGBA_STREAM_BLOCK), 0, st, p); } while (0)
-            switch (p.transfer) {
-            case AVIFGPU_TRANSFER_PQ:       if (pq_hi_launch(p)) AG_RGBA(kTransferPqHi); else AG_RGBA(AVIFGPU_TRANSFER_PQ); break;
-            case AVIFGPU_TRANSFER_HLG:      AG_RGBA(AVIFGPU_TRANSFER_HLG); break;
-            case AVIFGPU_TRANSFER_SMPTE428: AG_RGBA(AVIFGPU_TRANSFER_SMPTE428); break;
-            default:                        AG_RGBA(AVIFGPU_TRANSFER_CLIP); break;
-            }
-#undef AG_RGBA
-            return hipGetLastError();
-        }
-    }
-    const bool icc_lin = AG_ICC1_HOT && p.icc_trc_type[0] != 0 && p.icc_trc_linear[0] && p.icc_trc_linear[1] && p.icc_trc_linear[2];
-    const bool icc1 = icc_lin && p.icc_out == 0;
-    const bool icc4 = icc_lin && p.icc_out == 4 && p.transfer == AVIFGPU_TRANSFER_CLIP;
-    const bool icc2 = AG_ICC2_HOT && p.icc_trc_type[0] != 0 && p.icc_same_simple && p.icc_out == 0;
-    if ((variant & 1) && (p.icc_trc_type[0] == 0 || icc1 || icc4 || icc2) && depth == 32 && planes == 3 && dst16 && output == AVIFGPU_OUT_YCBCR && xs == 1 &&
-        // any width (round 4: buffer addressing clips the ragged lane in hardware); rows and planes dword-aligned
-        (p.src_row_bytes & 3) == 0 && (reinterpret_cast<uintptr_t>(p.src) & 3) == 0 &&
-        ((reinterpret_cast<uintptr_t>(p.dst[0]) | reinterpret_cast<uintptr_t>(p.dst[1]) | reinterpret_cast<uintptr_t>(p.dst[2]) |
-          (uintptr_t)p.dst_stride[0] | (uintptr_t)p.dst_stride[1] | (uintptr_t)p.dst_stride[2]) & 3) == 0) {
-        const long long spans = (long long)((p.width + 511) / 512) * ((p.nrows + (1 << ys) - 1) >> ys);
-        if (spans == 0) return hipSuccess;
-        if (spans + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            const int spw = (AG_SUB_SPW2 && ys == 0 && (p.width % 512) == 0 && spans >= AG_SUB_SPW2_MIN_SPANS) ? 2 : 1;      // spans per wave (see the kernel's loop)
-            const long long need = (spans + kF32Waves * spw - 1) / (kF32Waves * spw);
-            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / kF32Waves, variant);
-            snprintf(label, kLabelBytes, "write_rgb32_ycbcr_sub_hot<transfer=%d,xs=1,ys=%d>%s", p.transfer, ys, icc1 ? " icc=1" : icc4 ? " icc=4" : icc2 ? " icc=2" : "");
-            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / kF32Waves);
-#define AG_SUB3(TR, YS_, IC) do { if (p.nearest) hipLaunchKernelGGL((write_rgb32_ycbcr_sub_hot<TR, 1, YS_, IC, true>), dim3((int)blocks), dim3(AG_F32_STREAM_BLOCK), 0, st, p); \
-                                  else hipLaunchKernelGGL((write_rgb32_ycbcr_sub_hot<TR, 1, YS_, IC, false>), dim3((int)blocks), dim3(AG_F32_STREAM_BLOCK), 0, st, p); } while (0)
-#define AG_SUB2(TR, YS_) do { if (icc1) AG_SUB3(TR, YS_, 1); else if (icc2) AG_SUB3(TR, YS_, 2); else AG_SUB3(TR, YS_, 0); } while (0)
-#define AG_SUB(TR) do { if (ys) AG_SUB2(TR, 1); else AG_SUB2(TR, 0); } while (0)
-            if (icc4) {
-                if (ys) AG_SUB3(AVIFGPU_TRANSFER_CLIP, 1, 4); else AG_SUB3(AVIFGPU_TRANSFER_CLIP, 0, 4);
-                return hipGetLastError();
-            }
-            switch (p.transfer) {
-            case AVIFGPU_TRANSFER_PQ:       if (pq_hi_launch(p)) AG_SUB(kTransferPqHi); else AG_SUB(AVIFGPU_TRANSFER_PQ); break;
-            case AVIFGPU_TRANSFER_HLG:      AG_SUB(AVIFGPU_TRANSFER_HLG); break;
-            case AVIFGPU_TRANSFER_SMPTE428: AG_SUB(AVIFGPU_TRANSFER_SMPTE428); break;
-            default:                        AG_SUB(AVIFGPU_TRANSFER_CLIP); break;
-            }
-#undef AG_SUB
-#undef AG_SUB2
-            return hipGetLastError();
-        }
-    }
-    *taken = false;
-    return hipSuccess;
+    return hipGetLastError();
 }
 #endif
 
@@ -4371,13 +3904,9 @@ static hipError_t launch_hist_twin(const WriteParams& p, const HistParams& h, in
 template <int PLANES>
 static hipError_t launch_hist_tr(const WriteParams& p, const HistParams& h, int blocks, bool aligned, hipStream_t st)
 {
-    switch (p.transfer) {
-    case AVIFGPU_TRANSFER_PQ:       if (pq_hi_launch(p)) return launch_hist_icc<PLANES, kTransferPqHi>(p, h, blocks, aligned, st);
-                                    return launch_hist_icc<PLANES, 0>(p, h, blocks, aligned, st);
-    case AVIFGPU_TRANSFER_HLG:      return launch_hist_icc<PLANES, 1>(p, h, blocks, aligned, st);
-    case AVIFGPU_TRANSFER_SMPTE428: return launch_hist_icc<PLANES, 2>(p, h, blocks, aligned, st);
-    default:                        return launch_hist_icc<PLANES, 3>(p, h, blocks, aligned, st);
-    }
+    hipError_t e = hipErrorInvalidValue;
+    with_transfer(transfer_id(p), [&](auto tr) { e = launch_hist_icc<PLANES, AG_V(tr)>(p, h, blocks, aligned, st); });
+    return e;
 }
 
 // Entry used by avifgpu_api.hip / pipeline.hip behind launch_write() of the same tile: p as that launch got it (the plane pointers are
@@ -4410,189 +3939,77 @@ hipError_t launch_write_hist(const WriteParams& p0, int planes, unsigned long lo
 #endif   // AG_WRITE_PART == 0 || 40
 
 #if AG_WRITE_PART == 0 || AG_WRITE_PART == 1
-static hipError_t launch_write_impl(const WriteParams& p, int depth, int planes, bool dst16, int output, int xs, int ys,
-                                    int variant, hipStream_t st, char* label);
-
-// Entry used by avifgpu_api.hip.  `variant` selects the hot-path implementation when it applies.
-//
-// FLAT launches (round 3).  When nothing depends on where a row ends -- 4:4:4 or 4:2:2 planes or the interleaved hand-off, 16- /
-// 32-bit documents -- and source and planes are contiguous (row stride == row bytes: the library's own staging buffers whenever a row is a
-// multiple of 16 bytes, and any tightly packed caller buffer), the tile IS one long row of width x nrows pixels.  Launched as such,
-// every wave's span starts on a span boundary of the buffer instead of a row boundary: no half-empty last span per row (7952-wide
-// rows fill 15.53 spans of 512 pixels) and no rows that start in the middle of a 128-byte line (7952 x 12 B = 745.5 lines).  Same
-// kernels, same per-pixel arithmetic, same bytes (tests/test_gpu_kernel_equivalence.py); variant bit 4 (16) turns it off for A/B.
-#ifndef AG_FLAT
-#define AG_FLAT 1
+// this part's own launches: RGB f32 4:4:4 with and without a streaming ICC stage, and the f32 hand-off
+static hipError_t launch_stream_f32_444(const WriteParams& p, const WriteLaunch& L, int planes, hipStream_t st)
+{
+    const dim3 grid((int)L.blocks), f32(AG_F32_STREAM_BLOCK);
+    switch (L.kernel) {
+    case kWkRgb32IccRef:                            // the interleaved hand-off as the ICC kernel's output
+        if (L.icc == 4) hipLaunchKernelGGL((write_rgb32_icc1_ycbcr444_hot<AVIFGPU_TRANSFER_CLIP, 4, true>), grid, f32, 0, st, p);
+        else with_transfer(L.tr, [&](auto tr) {
+            if (L.icc == 2) hipLaunchKernelGGL((write_rgb32_icc1_ycbcr444_hot<AG_V(tr), 2, true>), grid, f32, 0, st, p);
+            else hipLaunchKernelGGL((write_rgb32_icc1_ycbcr444_hot<AG_V(tr), 1, true>), grid, f32, 0, st, p);
+        });
+        break;
+    case kWkF32Ref:
+        with_transfer(L.tr, [&](auto tr) {
+            if (planes == 4) hipLaunchKernelGGL((write_f32_ref_stream<AG_V(tr), 4>), grid, dim3(AG_F32_REF_BLOCK), 0, st, p);
+            else if (planes == 1) hipLaunchKernelGGL((write_f32_ref_stream<AG_V(tr), 1>), grid, dim3(AG_F32_REF_BLOCK), 0, st, p);
+            else hipLaunchKernelGGL((write_f32_ref_stream<AG_V(tr), 3>), grid, dim3(AG_F32_REF_BLOCK), 0, st, p);
+        });
+        break;
+    case kWkRgb32Icc:
+        if (L.icc == 4) hipLaunchKernelGGL((write_rgb32_icc1_ycbcr444_hot<AVIFGPU_TRANSFER_CLIP, 4>), grid, f32, 0, st, p);
+        else with_transfer(L.tr, [&](auto tr) {
+            if (L.icc == 2) hipLaunchKernelGGL((write_rgb32_icc1_ycbcr444_hot<AG_V(tr), 2>), grid, f32, 0, st, p);
+            else hipLaunchKernelGGL((write_rgb32_icc1_ycbcr444_hot<AG_V(tr), 1>), grid, f32, 0, st, p);
+        });
+        break;
+    case kWkRgb32: {                                // the headline
+        // measuring knob (not a tuning word of the product): AVIFGPU_DEBUG_LDS_PAD = bytes of unused dynamic LDS per workgroup, i.e. fewer
+        // resident workgroups per CU -- how the kernel's rate depends on the number of waves per SIMD (profiles/r05/occupancy_sweep_444.txt)
+        // Compiled in only with -DAG_MEASURE=1 (tools/ab_variants.sh): a product launch reads no environment variable.
+#if AG_MEASURE
+        static const size_t lds_pad = [] { const char* e = getenv("AVIFGPU_DEBUG_LDS_PAD"); const long v = e ? atol(e) : 0; return (size_t)(v < 0 ? 0 : (v > 140000 ? 140000 : v)); }();
+#else
+        constexpr size_t lds_pad = 0;
 #endif
+        with_transfer(L.tr, [&](auto tr) { with_bool(L.px8, [&](auto px8) { with_bool(L.nt, [&](auto nt) {
+            constexpr int pxl = AG_V(px8) ? 8 : 4;
+            if (L.lines) hipLaunchKernelGGL((write_rgb32_ycbcr444_hot<AG_V(tr), pxl, AG_V(nt), AG_HOT444_BLOCK_LINES>), grid, dim3(AG_HOT444_BLOCK_LINES), lds_pad, st, p);
+            else hipLaunchKernelGGL((write_rgb32_ycbcr444_hot<AG_V(tr), pxl, AG_V(nt), AG_HOT444_BLOCK>), grid, dim3(AG_HOT444_BLOCK), lds_pad, st, p);
+        }); }); });
+        break;
+    }
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// Entry used by avifgpu_api.hip.  `variant` is the tuning word (kernel_params.h): it selects the hot-path implementation where one
+// applies.  The decision -- the FLAT rule, the candidates in their order, the generic kernel's ICC stage, the grid, the label -- is
+// decide_write's; here it goes to the code object that holds its kernel.
 hipError_t launch_write(const WriteParams& p, int depth, int planes, bool dst16, int output, int xs, int ys,
                         int variant, hipStream_t st, char* label)
 {
-    const long long px = (long long)p.width * p.nrows;
-    // 4:2:2 qualifies too (chroma is sub-sampled along the row only): even width, chroma planes of width / 2 samples per row
-    const bool h422 = xs == 1 && ys == 0 && (p.width & 1) == 0 && output == AVIFGPU_OUT_YCBCR;
-    bool flat = AG_FLAT && (variant & 1) && !(variant & 16) && p.nrows > 1 && planes >= 3 && (depth == 16 || depth == 32) && ys == 0 && (xs == 0 || h422) &&
-                px < (1LL << 29) && p.src_row_bytes == (long long)p.width * planes * (depth / 8);
-    const int dsz = dst16 ? 2 : 1;
-    auto plane_px = [&](int pl, long long w) { return (h422 && (pl == 1 || pl == 2)) ? w / 2 : w; };
-    if (flat) {
-        if (output == AVIFGPU_OUT_REFERENCE) flat = p.dst_stride[0] == (long long)p.width * planes * dsz;
-        else for (int pl = 0; pl < (planes == 4 ? 4 : 3); ++pl) flat = flat && p.dst[pl] != nullptr && p.dst_stride[pl] == plane_px(pl, p.width) * dsz;
-    }
-    if (!flat) return launch_write_impl(p, depth, planes, dst16, output, xs, ys, variant, st, label);
-    WriteParams q = p;
-    q.width = (int32_t)px; q.nrows = 1; q.rows_to_end = 1;
-    q.src_row_bytes = px * planes * (depth / 8);
-    for (int pl = 0; pl < 4; ++pl) if (q.dst[pl]) q.dst_stride[pl] = (output == AVIFGPU_OUT_REFERENCE ? px * planes : plane_px(pl, px)) * dsz;
-    const hipError_t e = launch_write_impl(q, depth, planes, dst16, output, xs, ys, variant, st, label);
-    const size_t n = strlen(label);
-    if (n + 6 < (size_t)kLabelBytes) snprintf(label + n, kLabelBytes - n, " flat");
-    return e;
-}
-
-static hipError_t launch_write_impl(const WriteParams& p, int depth, int planes, bool dst16, int output, int xs, int ys,
-                                    int variant, hipStream_t st, char* label)
-{
-    // hot path: RGB f32 (no alpha) -> YCbCr 4:4:4 u16 with aligned rows; `variant` is a tuning word:
-    //   bit0 enable, bit1 PXL=8 (else 4), bit2 non-temporal, bit3 take the size-gated streaming kernels at any size (tests);
-    //   bits 8.. = a block cap below the launcher's own, for every capped launch of the library (0 = none; capped_blocks, staging.h).
-    // (8-bit documents stay on write_px: measured 0.057 vs 0.069 ms for the RGB8 copy, 0.090 vs 0.095 ms for RGBA8 premultiplied)
-    {   // 8- and 16-bit documents: part 2; f32 documents saved 4:2:2 / 4:2:0 or with transparency: part 3; the rest of this function: part 1
-        bool taken = false;
-        const hipError_t e = depth != 32 ? launch_stream_int(p, depth, planes, dst16, output, xs, ys, variant, st, label, &taken)
-                                         : launch_stream_f32_sub_rgba(p, depth, planes, dst16, output, xs, ys, variant, st, label, &taken);
-        if (taken) return e;
-    }
-    {   // ... behind a linear (or one simple parametric) document profile: the streaming ICC kernel with the interleaved hand-off as its output
-        const bool lin = AG_ICC1_HOT && p.icc_trc_type[0] != 0 && p.icc_s_tab == nullptr && p.icc_trc_linear[0] && p.icc_trc_linear[1] && p.icc_trc_linear[2];
-        const bool r1 = lin && p.icc_out == 0, r4 = lin && p.icc_out == 4 && p.transfer == AVIFGPU_TRANSFER_CLIP;
-        const bool r2 = AG_ICC2_HOT && p.icc_trc_type[0] != 0 && p.icc_s_tab == nullptr && p.icc_same_simple && p.icc_out == 0;
-        if ((variant & 1) && (r1 || r4 || r2) && depth == 32 && planes == 3 && dst16 && output == AVIFGPU_OUT_REFERENCE &&
-            (p.src_row_bytes & 3) == 0 && (reinterpret_cast<uintptr_t>(p.src) & 3) == 0 &&
-            ((reinterpret_cast<uintptr_t>(p.dst[0]) | (uintptr_t)p.dst_stride[0]) & 15) == 0) {
-            const long long spans = (long long)((p.width + 511) / 512) * p.nrows;
-            if (spans == 0) return hipSuccess;
-            if (spans + 8LL * 65536 * 4 < 0x7fffffffLL) {
-                const long long need = (spans + kF32Waves - 1) / kF32Waves;
-                const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / kF32Waves, variant);
-                snprintf(label, kLabelBytes, "write_rgb32_icc1_ycbcr444_hot<transfer=%d,out=ref> icc=%d", p.transfer, r4 ? 4 : r2 ? 2 : 1);
-                label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / kF32Waves);
-                if (r4) { hipLaunchKernelGGL((write_rgb32_icc1_ycbcr444_hot<AVIFGPU_TRANSFER_CLIP, 4, true>), dim3((int)blocks), dim3(AG_F32_STREAM_BLOCK), 0, st, p); return hipGetLastError(); }
-#define AG_IREF32(TR) do { if (r2) hipLaunchKernelGGL((write_rgb32_icc1_ycbcr444_hot<TR, 2, true>), dim3((int)blocks), dim3(AG_F32_STREAM_BLOCK), 0, st, p); \
-                           else hipLaunchKernelGGL((write_rgb32_icc1_ycbcr444_hot<TR, 1, true>), dim3((int)blocks), dim3(AG_F32_STREAM_BLOCK), 0, st, p); } while (0)
-                switch (p.transfer) {
-                case AVIFGPU_TRANSFER_PQ:       if (pq_hi_launch(p)) AG_IREF32(kTransferPqHi); else AG_IREF32(AVIFGPU_TRANSFER_PQ); break;
-                case AVIFGPU_TRANSFER_HLG:      AG_IREF32(AVIFGPU_TRANSFER_HLG); break;
-                case AVIFGPU_TRANSFER_SMPTE428: AG_IREF32(AVIFGPU_TRANSFER_SMPTE428); break;
-                default:                        AG_IREF32(AVIFGPU_TRANSFER_CLIP); break;
-                }
-#undef AG_IREF32
-                return hipGetLastError();
-            }
+    WriteParams one_row;                            // the tile of a FLAT launch; written only for one
+    WriteLaunch L;
+    decide_write(p, depth, planes, dst16, output, xs, ys, variant, one_row, L);
+    if (L.invalid) return hipErrorInvalidValue;
+    if (L.kernel == kWkEmpty) return hipSuccess;
+    memcpy(label, L.label, strlen(L.label) + 1);
+    const WriteParams& q = L.flat ? one_row : p;
+    if (L.kernel == kWkPx) {
+        switch (depth) {                            // the generic kernel: a code object per document depth
+        case 8:  return launch_planes_d8(q, planes, dst16, output, xs, ys, L, st);
+        case 16: return launch_planes_d16(q, planes, dst16, output, xs, ys, L, st);
+        default: return launch_planes_d32(q, planes, dst16, output, xs, ys, L, st);
         }
     }
-    // (round 5) ... and Gray32 -> Y plane: a gray document without alpha IS its Y plane sample for sample (WriteHeifImage.cpp:181-252), the same
-    // elementwise kernel with one sample per pixel (0.62 of 8 TB/s on the generic kernel)
-    if ((variant & 1) && p.icc_trc_type[0] == 0 && depth == 32 && ((planes >= 3 && output == AVIFGPU_OUT_REFERENCE) || planes == 1) && dst16 &&
-        ((long long)p.width * planes) % 4 == 0 && (p.src_row_bytes & 15) == 0 && (reinterpret_cast<uintptr_t>(p.src) & 15) == 0 &&
-        ((reinterpret_cast<uintptr_t>(p.dst[0]) | (uintptr_t)p.dst_stride[0]) & 7) == 0) {
-        const long long n4 = (long long)p.width * planes / 4;
-        const long long waves = ((n4 + 255) / 256) * p.nrows;
-        if (waves == 0) return hipSuccess;
-        if (waves + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            const long long need = (waves + kF32RefWaves - 1) / kF32RefWaves;
-            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / kF32RefWaves, variant);
-            snprintf(label, kLabelBytes, "write_f32_ref_stream<transfer=%d,planes=%d>", p.transfer, planes);
-            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / kF32RefWaves);
-#define AG_REF(TR) do { if (planes == 4) hipLaunchKernelGGL((write_f32_ref_stream<TR, 4>), dim3((int)blocks), dim3(AG_F32_REF_BLOCK), 0, st, p); \
-                        else if (planes == 1) hipLaunchKernelGGL((write_f32_ref_stream<TR, 1>), dim3((int)blocks), dim3(AG_F32_REF_BLOCK), 0, st, p); \
-                        else hipLaunchKernelGGL((write_f32_ref_stream<TR, 3>), dim3((int)blocks), dim3(AG_F32_REF_BLOCK), 0, st, p); } while (0)
-            switch (p.transfer) {
-            case AVIFGPU_TRANSFER_PQ:       if (pq_hi_launch(p)) AG_REF(kTransferPqHi); else AG_REF(AVIFGPU_TRANSFER_PQ); break;
-            case AVIFGPU_TRANSFER_HLG:      AG_REF(AVIFGPU_TRANSFER_HLG); break;
-            case AVIFGPU_TRANSFER_SMPTE428: AG_REF(AVIFGPU_TRANSFER_SMPTE428); break;
-            default:                        AG_REF(AVIFGPU_TRANSFER_CLIP); break;
-            }
-#undef AG_REF
-            return hipGetLastError();
-        }
-    }
-    const bool icc_lin = AG_ICC1_HOT && p.icc_trc_type[0] != 0 && p.icc_trc_linear[0] && p.icc_trc_linear[1] && p.icc_trc_linear[2];
-    const bool icc1 = icc_lin && p.icc_out == 0;
-    const bool icc4 = icc_lin && p.icc_out == 4 && p.transfer == AVIFGPU_TRANSFER_CLIP;
-    const bool icc2 = AG_ICC2_HOT && p.icc_trc_type[0] != 0 && p.icc_same_simple && p.icc_out == 0;
-    // ... and with a linear document profile in front (icc = 1)
-    if ((variant & 1) && (icc1 || icc4 || icc2) &&
-        depth == 32 && planes == 3 && dst16 && output == AVIFGPU_OUT_YCBCR && xs == 0 && ys == 0 &&
-        (p.src_row_bytes & 3) == 0 && (reinterpret_cast<uintptr_t>(p.src) & 3) == 0 &&
-        ((reinterpret_cast<uintptr_t>(p.dst[0]) | reinterpret_cast<uintptr_t>(p.dst[1]) | reinterpret_cast<uintptr_t>(p.dst[2]) |
-          (uintptr_t)p.dst_stride[0] | (uintptr_t)p.dst_stride[1] | (uintptr_t)p.dst_stride[2]) & 3) == 0) {
-        const long long spans = (long long)((p.width + 511) / 512) * p.nrows;
-        if (spans == 0) return hipSuccess;
-        if (spans + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            const long long need = (spans + kF32Waves - 1) / kF32Waves;
-            const long long blocks = capped_blocks(need, AG_STREAM_BLOCK_CAP * 4 / kF32Waves, variant);
-            snprintf(label, kLabelBytes, "write_rgb32_icc1_ycbcr444_hot<transfer=%d> icc=%d", p.transfer, icc4 ? 4 : icc2 ? 2 : 1);
-            label_cap(label, blocks, need, AG_STREAM_BLOCK_CAP * 4 / kF32Waves);
-            if (icc4) { hipLaunchKernelGGL((write_rgb32_icc1_ycbcr444_hot<AVIFGPU_TRANSFER_CLIP, 4>), dim3((int)blocks), dim3(AG_F32_STREAM_BLOCK), 0, st, p); return hipGetLastError(); }
-#define AG_I444(TR) do { if (icc2) hipLaunchKernelGGL((write_rgb32_icc1_ycbcr444_hot<TR, 2>), dim3((int)blocks), dim3(AG_F32_STREAM_BLOCK), 0, st, p); \
-                         else hipLaunchKernelGGL((write_rgb32_icc1_ycbcr444_hot<TR, 1>), dim3((int)blocks), dim3(AG_F32_STREAM_BLOCK), 0, st, p); } while (0)
-            switch (p.transfer) {
-            case AVIFGPU_TRANSFER_PQ:       if (pq_hi_launch(p)) AG_I444(kTransferPqHi); else AG_I444(AVIFGPU_TRANSFER_PQ); break;
-            case AVIFGPU_TRANSFER_HLG:      AG_I444(AVIFGPU_TRANSFER_HLG); break;
-            case AVIFGPU_TRANSFER_SMPTE428: AG_I444(AVIFGPU_TRANSFER_SMPTE428); break;
-            default:                        AG_I444(AVIFGPU_TRANSFER_CLIP); break;
-            }
-#undef AG_I444
-            return hipGetLastError();
-        }
-    }
-    if ((variant & 1) && p.icc_trc_type[0] == 0 && depth == 32 && planes == 3 && dst16 && output == AVIFGPU_OUT_YCBCR && xs == 0 && ys == 0 &&
-        (p.src_row_bytes & 3) == 0 && (reinterpret_cast<uintptr_t>(p.src) & 3) == 0 &&
-        ((reinterpret_cast<uintptr_t>(p.dst[0]) | reinterpret_cast<uintptr_t>(p.dst[1]) | reinterpret_cast<uintptr_t>(p.dst[2]) |
-          (uintptr_t)p.dst_stride[0] | (uintptr_t)p.dst_stride[1] | (uintptr_t)p.dst_stride[2]) & 3) == 0) {
-        {                                             // any width (round 4): the last span of a row is clipped by the buffer resources
-            const bool px8 = variant & 2, nt = variant & 4;
-            const int span_px = px8 ? 512 : 256;
-            const long long spans = (long long)((p.width + span_px - 1) / span_px) * p.nrows;
-            if (spans == 0) return hipSuccess;
-            if (spans + 8LL * 65536 * 4 < 0x7fffffffLL) {
-            // spans on 128-byte lines (a flat tile is one row): the two-wave workgroup; rows that start inside a line: the four-wave one
-            const uintptr_t bases = reinterpret_cast<uintptr_t>(p.src) | reinterpret_cast<uintptr_t>(p.dst[0]) | reinterpret_cast<uintptr_t>(p.dst[1]) | reinterpret_cast<uintptr_t>(p.dst[2]);
-            const uintptr_t strides = (uintptr_t)p.src_row_bytes | (uintptr_t)p.dst_stride[0] | (uintptr_t)p.dst_stride[1] | (uintptr_t)p.dst_stride[2];
-            const bool lines = (bases & 127) == 0 && (p.nrows == 1 || (strides & 127) == 0);
-            const int WPB = (lines ? AG_HOT444_BLOCK_LINES : AG_HOT444_BLOCK) / 64;
-            const long long need = (spans + WPB - 1) / WPB;
-            const long long cap = 256LL * 512 * 4 / WPB;                                      // 8192^2: one span per wave measured 5-6 % faster than two
-            const long long blocks = capped_blocks(need, cap, variant);
-            snprintf(label, kLabelBytes, "write_rgb32_ycbcr444_hot<transfer=%d,pxl=%d,nt=%d>", p.transfer, px8 ? 8 : 4, (int)nt);
-            label_cap(label, blocks, need, cap);
-            // measuring knob (not a tuning word of the product): AVIFGPU_DEBUG_LDS_PAD = bytes of unused dynamic LDS per workgroup, i.e. fewer
-            // resident workgroups per CU -- how the kernel's rate depends on the number of waves per SIMD (profiles/r05/occupancy_sweep_444.txt)
-            // Compiled in only with -DAG_MEASURE=1 (tools/ab_variants.sh): a product launch reads no environment variable.
-#if AG_MEASURE
-            static const size_t lds_pad = [] { const char* e = getenv("AVIFGPU_DEBUG_LDS_PAD"); const long v = e ? atol(e) : 0; return (size_t)(v < 0 ? 0 : (v > 140000 ? 140000 : v)); }();
-#else
-            constexpr size_t lds_pad = 0;
-#endif
-#define AG_HOT3(TR, PX, NT_) do { if (lines) hipLaunchKernelGGL((write_rgb32_ycbcr444_hot<TR, PX, NT_, AG_HOT444_BLOCK_LINES>), dim3((int)blocks), dim3(AG_HOT444_BLOCK_LINES), lds_pad, st, p); \
-                                  else hipLaunchKernelGGL((write_rgb32_ycbcr444_hot<TR, PX, NT_, AG_HOT444_BLOCK>), dim3((int)blocks), dim3(AG_HOT444_BLOCK), lds_pad, st, p); } while (0)
-#define AG_HOT2(TR, PX) do { if (nt) AG_HOT3(TR, PX, true); else AG_HOT3(TR, PX, false); } while (0)
-#define AG_HOT1(TR) do { if (px8) AG_HOT2(TR, 8); else AG_HOT2(TR, 4); } while (0)
-            switch (p.transfer) {
-            case AVIFGPU_TRANSFER_PQ:       if (pq_hi_launch(p)) AG_HOT1(kTransferPqHi); else AG_HOT1(AVIFGPU_TRANSFER_PQ); break;
-            case AVIFGPU_TRANSFER_HLG:      AG_HOT1(AVIFGPU_TRANSFER_HLG); break;
-            case AVIFGPU_TRANSFER_SMPTE428: AG_HOT1(AVIFGPU_TRANSFER_SMPTE428); break;
-            default:                        AG_HOT1(AVIFGPU_TRANSFER_CLIP); break;
-            }
-            return hipGetLastError();
-            }
-        }
-    }
-    switch (depth) {                                // the generic kernel: a code object per document depth
-    case 8:  return launch_planes_d8(p, planes, dst16, output, xs, ys, st, label);
-    case 16: return launch_planes_d16(p, planes, dst16, output, xs, ys, st, label);
-    default: return launch_planes_d32(p, planes, dst16, output, xs, ys, st, label);
-    }
+    // 8- and 16-bit documents: part 2; f32 documents saved 4:2:2 / 4:2:0 or with transparency: part 3; the rest: this part
+    if (L.kernel <= kWkRgb16Sub) return launch_stream_int(q, L, depth, planes, dst16, xs, ys, st);
+    if (L.kernel <= kWkRgb32Sub) return launch_stream_f32_sub_rgba(q, L, ys, st);
+    return launch_stream_f32_444(q, L, planes, st);
 }
 #endif   // AG_WRITE_PART == 0 || 1
 
