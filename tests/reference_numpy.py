@@ -118,6 +118,17 @@ def _clip_round(v, maxi):
     return np.clip(x.astype(np.int64), 0, maxi)                         # the cast truncates towards zero, like C's
 
 
+def stage_b_rows(kr, kb):
+    """The three rows of the RGB -> YCbCr matrix as float32, each coefficient rounded as oracle/avif_oracle.c:442-446 rounds it."""
+    kr, kb = F(kr), F(kb)
+    kg = F(1) - kr - kb
+    rows = {"y": (kr, kg, kb),
+            "cb": (-kr / (F(1) - kb) / F(2), -kg / (F(1) - kb) / F(2), F(0.5)),
+            "cr": (F(0.5), -kg / (F(1) - kr) / F(2), -kb / (F(1) - kr) / F(2))}
+    assert all(type(c) is np.float32 for r in rows.values() for c in r)
+    return rows
+
+
 def write8_code_tables(matrix, bits, primaries=1):
     """The 8-bit RGB -> Y, Cb, Cr 4:4:4 save for EVERY (r, g, b): three (256, 256, 256) tables of `bits`-bit codes indexed [r, g, b]
     (full range, libheif's chroma zero point 2^(bits-1): oracle/avif_oracle.c:427-448, :530-565)."""
@@ -129,11 +140,8 @@ def write8_code_tables(matrix, bits, primaries=1):
         return (np.broadcast_to(q[None, :, None], shape).astype(dt), np.broadcast_to(q[None, None, :], shape).astype(dt),
                 np.broadcast_to(q[:, None, None], shape).astype(dt))
     kr, kg, kb = coefficients(matrix, primaries)
-    kg = F(1) - kr - kb
     half = F(1 << (bits - 1))
-    rows = {"y": (kr, kg, kb),
-            "cb": (-kr / (F(1) - kb) / F(2), -kg / (F(1) - kb) / F(2), F(0.5)),
-            "cr": (F(0.5), -kg / (F(1) - kr) / F(2), -kb / (F(1) - kr) / F(2))}
+    rows = stage_b_rows(kr, kb)
     qf = q.astype(F)
     out = []
     for name in ("y", "cb", "cr"):
@@ -144,4 +152,97 @@ def write8_code_tables(matrix, bits, primaries=1):
             s = s + half
         assert s.dtype == np.float32
         out.append(_clip_round(s, maxi).astype(dt))
+    return tuple(out)
+
+
+# ---- 10- / 12-bit planes: the open to 16-bit host rows and the save of code triples, elementwise -------------------------------------
+# The tables above enumerate 8-bit inputs; 2^30 and 2^36 triples cannot be enumerated, so these two evaluate the same float32 lines on
+# the pixels they are given.  `mutant` names ONE deliberate departure from the reference's operations (tests/test_tie_inputs.py counts
+# what each changes); None is the reference.
+_LIMITED = {8: ((16, 235), (16, 240)), 10: ((64, 940), (64, 960)), 12: ((256, 3760), (256, 3840))}      # YuvLookupTables.cpp:69-109
+
+
+def read_tables(bits, full_range, identity=False):
+    """(table Y, table UV, table A): 2^bits float32 entries each (YuvLookupTables.cpp:157-190)."""
+    full = (1 << bits) - 1
+    i = np.arange(full + 1, dtype=np.int64)
+    uy, uuv = i, i
+    if not full_range:
+        (ylo, yhi), (clo, chi) = _LIMITED[bits]
+        uy = limited_to_full(i, ylo, yhi, full)
+        uuv = limited_to_full(i, clo, chi, full)
+    ty = uy.astype(F) / F(full)
+    tuv = ty if identity else uuv.astype(F) / F(full) - F(0.5)
+    ta = i.astype(F) / F(full)
+    assert ty.dtype == tuv.dtype == ta.dtype == np.float32
+    return ty, tuv, ta
+
+
+def fused(a, b, c):
+    """a * b + c with ONE rounding, as a contracted multiply-add gives it: the product of two float32 is exact in float64 and the
+    sum is rounded to float64 before it is rounded to float32 (a double rounding that differs from the fused result on about one
+    input in 2^29: this is a mutant, not a model of anything)."""
+    return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(F)
+
+
+def read16_rgb(planes, bits, matrix, full_range, primaries=1, alpha=None, shifts=(0, 0), mutant=None):
+    """(H, W * channels) u16 rows of a YCbCr open to the 16-bit host (YuvDecode.cpp:312-326, :369-388, :515 as
+    oracle/avif_oracle.c:751-782 restates them).  `planes`: {0: Y, 1: Cb, 2: Cr[, 3: A]}, chroma sub-sampled by `shifts` = (xs, ys)
+    and taken nearest; alpha: None, 'straight' or 'premultiplied'.  mutant: 'reciprocal' (x * (1 / kg) for x / kg) or 'fma' (the
+    chroma sum of G as one contracted multiply-add)."""
+    assert mutant in (None, "reciprocal", "fma") and alpha in (None, "straight", "premultiplied")
+    kr, kg, kb = coefficients(matrix, primaries)
+    ty, tuv, ta = read_tables(bits, full_range, identity=(matrix == GBR))
+    maxc = (1 << bits) - 1
+    xs, ys = shifts
+    up = lambda a: np.repeat(np.repeat(a, 1 << ys, axis=0), 1 << xs, axis=1) if (xs or ys) else a
+    y, cb, cr = ty[np.minimum(planes[0], maxc)], tuv[np.minimum(up(planes[1]), maxc)], tuv[np.minimum(up(planes[2]), maxc)]
+    one, two = F(1), F(2)
+    r = y + (two * (one - kr)) * cr                                     # :312
+    b = y + (two * (one - kb)) * cb                                     # :313
+    t_r = (kr * (one - kr)) * cr
+    s = fused(kb * (one - kb), cb, t_r) if mutant == "fma" else t_r + (kb * (one - kb)) * cb
+    num = two * s
+    g = y - (num * (one / kg) if mutant == "reciprocal" else num / kg)  # :314
+    out = np.empty(y.shape + (3 if alpha is None else 4,), dtype=np.uint16)
+    if alpha is not None:
+        ua = np.minimum(planes[3], maxc)
+        av = ta[ua]
+    for k, v in enumerate((r, g, b)):
+        v = np.minimum(np.maximum(v, F(0)), one)                        # std::clamp
+        if alpha == "premultiplied":                                    # :369-388: min(v * 1 / A, 1) under a translucent alpha, 0 under alpha 0
+            with np.errstate(divide="ignore", invalid="ignore"):
+                u = np.minimum((v * one) / av, one)
+            v = np.where(ua < maxc, np.where(ua == 0, F(0), u), v)
+        c = F(0.5) + (v * F(32768))
+        assert c.dtype == np.float32
+        out[..., k] = c.astype(np.uint16)                               # 0.5 <= c <= 32768.5: the cast truncates
+    if alpha is not None:
+        out[..., 3] = (F(0.5) + (av * F(32768))).astype(np.uint16)      # :515
+    return out.reshape(y.shape[0], -1)
+
+
+def write_codes_ycbcr(r, g, b, bits, matrix, primaries=1, mutant=None):
+    """(Y, Cb, Cr) codes of the `bits`-bit code planes r, g, b at full resolution (oracle/avif_oracle.c:534, :561-564; full range,
+    chroma zero point 2^(bits-1)).  mutant: 'fma' (the last product of each sum contracted into the addition) or 'reassociated'
+    (R c0 + (G c1 + B c2) for (R c0 + G c1) + B c2)."""
+    assert mutant in (None, "fma", "reassociated")
+    maxi = (1 << bits) - 1
+    kr, kg, kb = coefficients(matrix, primaries)
+    rows = stage_b_rows(kr, kb)
+    rf, gf, bf = (np.asarray(v).astype(F) for v in (r, g, b))
+    half = F(1 << (bits - 1))
+    out = []
+    for name in ("y", "cb", "cr"):
+        c0, c1, c2 = rows[name]
+        if mutant == "fma":
+            s = fused(bf, c2, rf * c0 + gf * c1)
+        elif mutant == "reassociated":
+            s = rf * c0 + (gf * c1 + bf * c2)
+        else:
+            s = (rf * c0 + gf * c1) + bf * c2
+        if name != "y":
+            s = s + half
+        assert s.dtype == np.float32
+        out.append(_clip_round(s, maxi).astype(np.uint16))
     return tuple(out)

@@ -12,7 +12,8 @@ run over the whole domain of each proof:
                on the Latin square under an alpha plane that takes every code in every row and column
   IEEE division (tuning bit 128) on the 12-bit Latin square and the 8-bit BT.709 triples
 
-NOT exhaustive: 10- and 12-bit TRIPLES (2^30, 2^36) -- G's final subtraction Y - term is seen for n^2 of them.
+10- and 12-bit TRIPLES: G's final subtraction Y - term is seen here for n^2 of them; tests/test_zzzzzzzzz_gpu_tie_triples.py adds, for
+every (Cb, Cr) pair, the Y that puts G next to a rounding tie.  NOT exhaustive: ALL 10- and 12-bit triples (2^30, 2^36).
 Every case asserts from the launch label that the intended kernel form ran.  Inputs: tests/exhaustive_inputs.py, whose coverage claims
 tests/test_exhaustive_inputs.py counts; the oracle itself is held to a numpy restatement of the reference there.
 The file is named to be collected after every earlier GPU test, so that those keep their places in the collection order.

@@ -12,7 +12,9 @@ exact_premultiply_fast_pair) in place of the float one, the 16 -> n bit rescale 
                         tools/divcheck_premul.hip -- through every kernel that premultiplies; straight alpha next to it
 
 Each case runs the streaming kernel the dispatcher picks AND the generic write_px (tuning word 0) against ONE oracle run, and asserts
-from the launch label which kernel ran.  NOT exhaustive: 16-bit SOURCE triples (2^45), 10- / 12-bit code triples.
+from the launch label which kernel ran.  10- / 12-bit code triples under a real matrix: tests/test_zzzzzzzzz_gpu_tie_triples.py holds, for
+every (R, B) pair, the G that puts Y, Cb or Cr next to a rounding tie.  NOT exhaustive: ALL 10- / 12-bit code triples (2^30, 2^36),
+16-bit SOURCE triples (2^45).
 Inputs: tests/exhaustive_inputs.py (claims counted in tests/test_exhaustive_inputs.py, where the oracle's save is also held to a numpy
 restatement on all triples).
 The file is named to be collected after every earlier GPU test, so that those keep their places in the collection order.
@@ -48,8 +50,8 @@ def _assert_kernel(label, d, variant, kernel):
     if variant == STREAMING and kernel is not None:
         begin, part = kernel if isinstance(kernel, tuple) else (kernel, "")
         assert label.startswith(begin) and part in label, (label, kernel)
-        # launch_write: contiguous 16-bit rows without vertical sub-sampling are one long row; so is a contiguous copy
-        flat = (d.depth == 16 and d.planes >= 3 and ys == 0) or begin.startswith("write_copy_rows_stream")
+        # launch_write: contiguous 16- and 32-bit rows without vertical sub-sampling are one long row; so is a contiguous copy
+        flat = (d.depth in (16, 32) and d.planes >= 3 and ys == 0) or begin.startswith("write_copy_rows_stream")
         assert label.endswith(" flat") == flat, label
     else:
         assert label.startswith(f"write_px<depth={d.depth},planes={d.planes},"), label
